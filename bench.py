@@ -14,18 +14,21 @@ A *step* is `--batches-per-step` batches (default 96 ≈ 50 ms of GPU work) of e
 `--steps 20` times ≈ 1 s and the clocks settle.  `value` = input IQ samples consumed per second over all ranks (inputs
 already in HBM).
 
-After the clock stops the LAST batch of the timed region is verified against the CPU oracle (`verified` in the JSON
+A plain run sets up (buffer placement included), warms up, times the steps and prints the headline line.  With --full,
+after the clock stops the LAST batch of the timed region is verified against the CPU oracle (`verified` in the JSON
 line): the fir_filter output bit for bit, the soft symbols against the oracle's serial receiver started from the very
 loop state the device used for that batch (snapshot taken in stream order), under the tolerance of the tiled mode
-(tests/test_gpu_rx_tiled.py).
+(tests/test_gpu_rx_tiled.py); --full also adds `unplaced`, `cpu_baseline` and `more` (below).
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (dump_outputs), so that two builds can be
+compared output for output: the same arguments give the same inputs.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 `--gpus N` without a launcher starts the N ranks itself.  N>1: independent captures, one process per GPU, no data-path
 collective, no RCCL (gloo carries the barrier and three scalars) -> weak scaling.
 
 Extra JSON objects: `roofline` for the dominant kernel (fir_filter; algorithmic bytes = 8 B read per input sample +
-8/30 B written) timed with HIP events on the kernel's own stream, `cpu_baseline` = the reference's blocks
+8/30 B written) timed with HIP events on the kernel's own stream; with --full `cpu_baseline` = the reference's blocks
 (oracle/_ref, or the plain-C oracle) timed on this host's cores on a bounded sample of the same workload, and `more` =
 the other configurations (single stream, carrier offset, full chain ...), each measured after the headline region.
 """
@@ -748,6 +751,35 @@ def emit(out):
     print(compact_line(out), flush=True)
 
 
+DUMP_LIMIT = 64 << 20       # bytes of --dump-outputs files in all (every rank together)
+DUMP_DECIMATED = 1 << 20    # decimated-stream samples kept per capture (a fixed, seeded sample of the batch's output)
+
+
+def dump_outputs(pipe, out_dir, rank=0, world=1):
+    """--dump-outputs: what the timed path computed in its LAST batch, as a caller of the pipeline receives it — every capture's
+    soft symbols (columns cost, symbol) and a fixed sample of its decimated stream (the fir_filter output: columns re, im; the
+    indices come from a seeded generator, the same for the same geometry) — written as float32 .npy files.  Rows beyond the
+    byte budget are sampled the same way."""
+    capi, g = pipe.capi, pipe.geo
+    os.makedirs(out_dir, exist_ok=True)
+    i = (pipe.batch_no - 1) % g["nbuf"]             # the decimated-stream buffer of the last batch
+    n_dec = g["n_out"] + pipe.extra
+    arrays = {}
+    for c, cp in enumerate(pipe.caps):
+        sym = pipe.ctx.download(cp.d_sym, capi.SOFTSYM, cp.last_produced)
+        arrays[f"c{c}_soft_symbols"] = np.stack([sym["cost"].astype(np.float32), sym["symbol"].astype(np.float32)], axis=1)
+        idx = np.sort(np.random.default_rng(1234).choice(n_dec, min(DUMP_DECIMATED, n_dec), replace=False))
+        y = pipe.ctx.download(cp.dec[i], np.complex64, n_dec)[idx]
+        arrays[f"c{c}_decimated_sample"] = np.stack([y.real, y.imag], axis=1).astype(np.float32)
+    budget = DUMP_LIMIT // max(1, world) // max(1, len(arrays)) - 4096          # (room for the .npy header)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays.items():
+        if a.nbytes > budget:
+            keep = budget // (a.itemsize * a.shape[1])
+            a = a[np.sort(np.random.default_rng(4321).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -770,10 +802,17 @@ def main():
                                                                  "instead of shared launches on one stream (lsdr_rx_run_multi_async)")
     ap.add_argument("--rx-cus", type=int, default=0, help="compute units reserved for the receiver streams (0: no partition)")
     ap.add_argument("--cu-pattern", choices=["xcd_major", "interleaved"], default="xcd_major")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: besides the headline, measure and check everything else — the CPU baseline, the unplaced pass, the oracle check of "
+                         "the timed output (`verified`) and the secondary configurations (`more`).  Without it a run sets up, warms up, times "
+                         "--steps steps and reports the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2: after the timed steps write what the last step computed (soft symbols of its last batch, a fixed sample of the "
+                         "decimated stream) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-more", action="store_true", help="skip the secondary configurations (`more` in the JSON line)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the oracle check of the timed output")
+    ap.add_argument("--no-more", action="store_true", help="with --full: skip the secondary configurations (`more` in the JSON line)")
     ap.add_argument("--dry-run", action="store_true", help="launch/aggregation plumbing only: no GPU work")
     ap.add_argument("--workload", choices=["c2", "c1"], default="c2",
                     help="c2: BASELINE config 2 (the headline: cf32 at 120 sps, fir_filter + receiver); c1: BASELINE config 1 / 4 — independent "
@@ -816,6 +855,8 @@ def main():
         return
 
     if args.workload == "c1":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is implemented for the c2 workload only")
         if args.c1_mode == "chain":
             # rounds 2-5: 16 worker streams — by default the HIP runtime multiplexes a process's streams onto 4 hardware queues, and two
             # captures whose kernels share a queue run one after the other.  One queue per worker: 123 -> 139 GS/s.  The batch engine
@@ -834,11 +875,11 @@ def main():
         sys.exit(rc)
 
     from leansdr_amd import synth
-    if rank == 0 and world == 1 and not args.no_more and (not os.environ.get("LSDR_BENCH_MORE_ONLY") or "c1" in os.environ["LSDR_BENCH_MORE_ONLY"].split(",")):
+    if rank == 0 and world == 1 and args.full and not args.no_more and (not os.environ.get("LSDR_BENCH_MORE_ONLY") or "c1" in os.environ["LSDR_BENCH_MORE_ONLY"].split(",")):
         import bench_more
         bench_more.c1_early(args)      # (the config-1/4 entry of `more`: a process of its own, before this one holds a context on the GPU)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:     # before the GPU is touched: the CPU workers are forked
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:     # before the GPU is touched: the CPU workers are forked
         order, fcut, decim0 = c2_design()
         c0 = _oracle().Oracle().lowpass(order, fcut)
         g0 = c2_geometry(args.batch_msamples, args.period_msamples, len(c0), decim0)
@@ -863,7 +904,7 @@ def main():
     unplaced = None
     n_cand = int(os.environ.get("LSDR_BENCH_PLACEMENT", 40))
     if args.captures == 1 and n_cand > 1 and (not os.environ.get("LSDR_RANK_DEVICES") or os.environ.get("LSDR_BENCH_PLACE_SHARED")):
-        if world == 1 and os.environ.get("LSDR_BENCH_UNPLACED", "1") != "0":      # (0: profiling runs — fewer launches that are not the timed region's)
+        if world == 1 and args.full and os.environ.get("LSDR_BENCH_UNPLACED", "1") != "0":      # (0: profiling runs — fewer launches that are not the timed region's)
             pipe.run(args.warmup * bps, False)
             pipe.sync()
             t0 = time.perf_counter()
@@ -875,22 +916,30 @@ def main():
                         "avg_launch_ms": r_un["avg_launch_ms"], "frac": r_un["frac"], "what": "the same pipeline and step count over the buffers as hipMalloc returned them, before placement"}
             pipe.fir_ms = []
         pipe.placement = pipe.place_buffers(n_cand)
+        # the batches played above moved the receivers' loop state by a number of batches that depends on timing: start again
+        # from the acquired state, so that the warm-up and the timed steps see the same stream state from run to run
+        for cp in pipe.caps:
+            cp.rx.reset()
+            cp.acquire(pipe.fir, pipe.rx_kw)
 
     pipe.run(args.warmup * bps, False)
     pipe.sync()
     shard.barrier()
     t0 = time.perf_counter()
-    consumed = pipe.run(args.steps * bps, True, snapshot_last=not args.no_verify)
+    verify = args.full and not args.no_verify
+    consumed = pipe.run(args.steps * bps, True, snapshot_last=verify)
     pipe.sync()
     shard.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(pipe, args.dump_outputs, rank, world)
 
     total, dt, _ = shard.aggregate(consumed, dt)   # all ranks' samples ÷ the slowest rank's time
 
     # EVERY rank checks its own captures against the oracle and contributes its verdict (gloo); rank 0 reports the job's
     rc = 0
     verified = None
-    if not args.no_verify:
+    if verify:
         verified = pipe.verify_last_batch()
         ranks_ok, ranks = shard.all_ranks_ok(verified["pass"])
         if not verified["pass"]:
@@ -944,7 +993,7 @@ def main():
     pipe.close()
 
     if rank == 0:
-        if world == 1 and not args.no_more:
+        if world == 1 and args.full and not args.no_more:
             import bench_more
             out["more"] = bench_more.run_all(capi, synth, local_rank, args)
         if cpu is not None:   # reported at N=1 only

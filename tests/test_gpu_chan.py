@@ -100,7 +100,7 @@ import os
 import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 APPS = os.path.join(ROOT, "leansdr_amd", "host", "apps")
-RG = os.path.join(ROOT, "leansdr_amd", "host", "ref_graph")
+RG = os.path.join(ROOT, "oracle", "_ref", "ref_graph")
 
 
 @pytest.mark.parametrize("name,args,kw", po.CHAN_CASES)
@@ -117,7 +117,7 @@ def test_leanchansim_amd_is_leanchansim(name, args, kw, buf):
     assert hashlib.sha256(y.tobytes()).digest() == bytes(g[name + "_sha"])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "leansdr_amd", "host", "ref_graph", "leandvb")), reason="ref_graph/leandvb not built")
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ref_graph", "leandvb")), reason="ref_graph/leandvb not built")
 def test_generator_pipeline_on_gpu():
     """test/leandvb_bench.sh:52-56 with every stage on the GPU: TS → leandvbtx_amd → leanchansim_amd (noise + LO drift) →
     leandvb (the reference's source on the GPU headers, throughput receiver) returns the transmitted packets."""

@@ -1,5 +1,5 @@
 """The C++ host framework (leansdr_amd/host: scheduler / pipebuf / shim blocks with the reference's class surface) driving the
-HIP kernels through the C ABI, end to end through the REFERENCE'S OWN graph builder: leansdr_amd/host/ref_graph/leandvb is
+HIP kernels through the C ABI, end to end through the REFERENCE'S OWN graph builder: oracle/_ref/ref_graph/leandvb is
 /root/reference/src/apps/leandvb.cc compiled unchanged against this repo's host headers (tests/test_gpu_ref_graph.py checks it
 byte for byte against the reference binary; here the transport stream is checked against the oracle chain, for several pipe
 sizes and for the throughput modes, which the reference's command line has no option for: they come from the environment,
@@ -13,15 +13,15 @@ from conftest import gold, bits_equal, ROOT
 import pyoracle as po
 
 pytestmark = [pytest.mark.gpu]
-APP = os.path.join(ROOT, "leansdr_amd", "host", "ref_graph", "leandvb")
+APP = os.path.join(ROOT, "oracle", "_ref", "ref_graph", "leandvb")
 
 
 @pytest.fixture(autouse=True, scope="module")
 def _receiver_cli_must_exist():
-    """The receiver CLI of this repo IS the reference's leandvb.cc compiled against leansdr_amd/host (`make -C leansdr_amd/host
-    ref_graph`, done by __graft_entry__.build() where /root/reference exists; the binary travels to the GPU box).  On a GPU box
+    """The receiver CLI of this repo IS the reference's leandvb.cc compiled against leansdr_amd/host (`make -C oracle ref_graph`,
+    done by __graft_entry__.build() where the reference sources are; the binary travels with oracle/_ref).  On a GPU box
     without it every full-chain test of this module would be skipped silently — fail instead."""
-    assert os.path.exists(APP), (f"{APP} is missing: build it where the reference sources are (make -C leansdr_amd/host ref_graph, "
+    assert os.path.exists(APP), (f"{APP} is missing: build it where the reference sources are (make -C oracle ref_graph, "
                                  "or python -c 'import __graft_entry__ as g; g.build()') — the full-chain tests cannot run without it")
 C1 = ["--u8", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2"]
 

@@ -15,7 +15,7 @@ def _run(extra, ranks=2, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["LSDR_RANK_DEVICES"] = ",".join(["0"] * ranks)
     env.update(env_extra or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--no-cpu", "--no-more"] + extra,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-more"] + extra,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]

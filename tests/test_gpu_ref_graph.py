@@ -1,10 +1,10 @@
 """The drop-in boundary, tried for real (north_star: "the existing leandvb graph drops in unchanged").
 
-leansdr_amd/host/ref_graph/{leandvb,leandvbtx,leanchansim,leantsgen} are the REFERENCE'S OWN app sources
-(/root/reference/src/apps/*.cc, compiled where they lie, unmodified, by leansdr_amd/host/Makefile) built against this repo's
+oracle/_ref/ref_graph/{leandvb,leandvbtx,leanchansim,leantsgen} are the REFERENCE'S OWN app sources
+(the reference's src/apps/*.cc, compiled where they lie, unmodified, by oracle/Makefile) built against this repo's
 host headers instead of the reference's: the same graph-building code, the same three-argument pipebufs, host file_reader /
 file_writer / printers — and every DSP/FEC block a GPU block behind the C ABI.  Pipes with a host end and a device end carry
-their items over PCIe by themselves (framework.h).  The binaries travel to the GPU box like oracle/_ref (built artefacts,
+their items over PCIe by themselves (framework.h).  The binaries live under oracle/_ref and travel with it (built artefacts,
 git-ignored); where they are missing the tests are skipped, not faked."""
 import hashlib
 import os
@@ -15,7 +15,7 @@ import pytest
 from conftest import gold, bits_equal, ROOT
 
 pytestmark = pytest.mark.gpu
-RG = os.path.join(ROOT, "leansdr_amd", "host", "ref_graph")
+RG = os.path.join(ROOT, "oracle", "_ref", "ref_graph")
 need_graph = pytest.mark.skipif(not os.path.exists(os.path.join(RG, "leandvb")), reason="ref_graph binaries not built (no /root/reference on the build machine)")
 
 BENCH_CASES = [("sps12", "6/5", 18, "", 700), ("sps4_viterbi_rrc", "4", 5.5, "--viterbi --sampler rrc", 500),
@@ -81,7 +81,7 @@ def test_reference_leandvb_other_input_formats(oracle, fmt, dtype, zero):
 # ---- same command line, same bytes: the reference's leandvb binary vs its source on the GPU headers ----------------------
 REFBIN = os.path.join(ROOT, "oracle", "_ref", "leandvb")
 need_both = pytest.mark.skipif(not (os.path.exists(os.path.join(RG, "leandvb")) and os.path.exists(REFBIN)),
-                               reason="needs leansdr_amd/host/ref_graph/leandvb and oracle/_ref/leandvb (built where /root/reference exists)")
+                               reason="needs oracle/_ref/ref_graph/leandvb and oracle/_ref/leandvb (built where the reference sources are)")
 C1 = ["--u8", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2"]
 
 

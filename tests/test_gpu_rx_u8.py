@@ -188,7 +188,7 @@ def test_deconv_on_packed_symbols(capi, ctx, rate, offset):
     a.close(); b.close(); d_soft.free(); d_words.free(); oa.free(); ob.free()
 
 
-def test_lds_staged_tiles_stop_where_their_32_bit_offsets_end(capi, ctx, oracle, capture, monkeypatch):
+def test_lds_staged_tiles_stop_where_their_32_bit_offsets_end(capi, ctx, oracle, capture, monkeypatch, tmp_path):
     """The LDS-staged cu8 tiles address samples through 32-bit buffer offsets: a run longer than that span is CUT (partial
     `consumed`), never decoded from zeros.  With the span mocked to 64 KiB a capture is consumed in several runs whose symbols,
     concatenated, track the serial receiver like one run does."""
@@ -216,8 +216,8 @@ while True:
     assert o["consumed"] * 2 + 64 <= (1 << 16) + 2 * 1024, o["consumed"]
     pos += o["consumed"]; runs += 1; syms.append(o["sym"]["symbol"].copy())
 print(json.dumps(dict(pos=pos, runs=runs, sym=np.concatenate(syms).tolist())))
-""" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "/tmp/lsdr_span_capture.u8", float(OMEGA))
-    np.asarray(capture, np.uint8).tofile("/tmp/lsdr_span_capture.u8")
+""" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), str(tmp_path / "span_capture.u8"), float(OMEGA))
+    np.asarray(capture, np.uint8).tofile(str(tmp_path / "span_capture.u8"))
     out = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300,
                          env=dict(os.environ, LSDR_RX_LDS_SPAN=str(1 << 16)))
     assert out.returncode == 0, out.stderr.decode()[-2000:]

@@ -7,7 +7,7 @@ import pytest
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-RG = os.path.join(ROOT, "leansdr_amd", "host", "ref_graph", "leandvb")
+RG = os.path.join(ROOT, "oracle", "_ref", "ref_graph", "leandvb")
 REF = os.path.join(ROOT, "oracle", "_ref", "leandvb")
 need = pytest.mark.skipif(not (os.path.exists(RG) and os.path.exists(REF)), reason="reference-built binaries absent (no /root/reference on the build machine)")
 

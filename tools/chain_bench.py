@@ -34,7 +34,7 @@ for w in ("--ref-graph", "--ref-cpu"):      # the reference's leandvb.cc on this
         flags.remove(w); which = w
 env = dict(os.environ)
 if which == "--ref-graph":
-    app = os.path.join(ROOT, "leansdr_amd", "host", "ref_graph", "leandvb")
+    app = os.path.join(ROOT, "oracle", "_ref", "ref_graph", "leandvb")
     if "--tiled" in flags:
         flags.remove("--tiled"); env["LSDR_TILED"] = "1"
     flags += ["--buf-factor", "4096"]

@@ -2,7 +2,7 @@
 # tools/headline_repeat.sh [n] ["extra bench.py arguments"] — the C2 headline n times back to back (processes of one box): value, filter launch, the unplaced figure, what lsdr_arena_place saw
 cd "$(dirname "$0")/.."
 for r in $(seq 1 ${1:-4}); do
-  timeout 300 python bench.py --no-more --no-cpu $2 2>/dev/null > /dev/null
+  timeout 300 python bench.py --full --no-more --no-cpu $2 2>/dev/null > /dev/null
   python - <<PY
 import json
 d=json.load(open("bench_full.json"))

@@ -31,7 +31,7 @@ RX_ENV = {}     # environment of the receiver process (LSDR_TILED=1, LSDR_FIR_AR
 def commands(ratio, snr, flags, ref=False):
     """The three command lines of one run (leandvb_bench.sh:20-56).  ref: False = this repo's apps, True = the reference
     binaries (oracle/_ref), "graph" = the reference's own app SOURCES compiled unchanged against this repo's host headers
-    (leansdr_amd/host/ref_graph: every block a GPU block)."""
+    (oracle/_ref/ref_graph: every block a GPU block)."""
     num, _, den = ratio.partition("/")
     r = float(num) / float(den or 1)
     symbrate = 1000000
@@ -42,14 +42,14 @@ def commands(ratio, snr, flags, ref=False):
     else:       # fixed noise floor, display scale adjusted
         sigpow, noisepow, scale = snr, 0, 10 * math.sqrt(r)
     if ref == "graph":
-        d = os.path.join(ROOT, "leansdr_amd", "host", "ref_graph")
+        d = os.path.join(ROOT, "oracle", "_ref", "ref_graph")
         tx, ch, rx = f"{d}/leandvbtx", f"{d}/leanchansim", f"{d}/leandvb"
     elif ref:
         d = os.path.join(ROOT, "oracle", "_ref")
         tx, ch, rx = f"{d}/leandvbtx", f"{d}/leanchansim", f"{d}/leandvb"
     else:
         d = os.path.join(ROOT, "leansdr_amd", "host", "apps")      # this repo's own generator-side builders; the receiver is always the
-        tx, ch, rx = f"{d}/leandvbtx_amd", f"{d}/leanchansim_amd", os.path.join(ROOT, "leansdr_amd", "host", "ref_graph", "leandvb")   # reference's source
+        tx, ch, rx = f"{d}/leandvbtx_amd", f"{d}/leanchansim_amd", os.path.join(ROOT, "oracle", "_ref", "ref_graph", "leandvb")   # reference's source
     cnr = "--cnr" if samprate > 3 * symbrate else ""
     c_tx = f"{tx} -f {ratio} --power {sigpow:g} --agc"
     c_ch = f"{ch} --awgn {noisepow:g} --deterministic {'--ou8' if hs else ''}"

@@ -11,7 +11,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/${1:-prof}
 mkdir -p "$OUT"
 cd "$REPO"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/prof_stats

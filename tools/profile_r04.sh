@@ -14,7 +14,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/${1:-r04_prof}
 mkdir -p "$OUT"
 cd "$REPO"; export TMPDIR=/tmp
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 python tools/bench_brief.py < "$OUT/bench.json" 2>/dev/null | tail -25
 cd /tmp; rm -rf /tmp/prof_stats
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python "$REPO/bench.py" --steps 20 --warmup 5 --no-cpu --no-more --no-verify > /tmp/prof_stats.log 2>&1

@@ -20,7 +20,7 @@ OUT=$REPO/gpurun_out/${1:-r05_prof}
 mkdir -p "$OUT"
 cd "$REPO"; export TMPDIR=/tmp
 MEASURE_LIB=$REPO/tools/variants/liblsdr_hip_measure.so
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 cp bench_full.json "$OUT/bench_full.json" 2>/dev/null
 python tools/bench_brief.py < "$OUT/bench.json" 2>/dev/null | tail -25
 cd /tmp; rm -rf /tmp/prof_stats

@@ -15,7 +15,7 @@ for k, v in d.items():
 PY
 cat gpurun_out/r06_prof_rx_alone.txt
 for w in 256 128; do
-  timeout 300 python bench.py --no-more --no-cpu --tile-warmup $w 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-more --no-cpu --tile-warmup $w 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('warmup $w', j['value'], j['roofline']['frac'], j['roofline']['avg_launch_ms'], j['verified'])"

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 for r in 1 2; do
 for g in "256 256" "256 128" "384 128" "512 128" "512 256" "384 256"; do
   set -- $g
-  timeout 300 python bench.py --no-more --no-cpu --tile-len $1 --tile-warmup $2 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-more --no-cpu --tile-len $1 --tile-warmup $2 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 v=j['verified']
