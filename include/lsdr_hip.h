@@ -494,6 +494,45 @@ int lsdr_viterbi_q4_supported(int cstln, int rate);
 int lsdr_viterbi_run(lsdr_viterbi *v, const lsdr_softsymbol *in, size_t n_in, uint8_t *out, size_t cap_out,
                      size_t *consumed, size_t *produced);
 
+/* ---- viterbi_sync for many streams at once: n_streams independent decoders (each one a viterbi_sync of its own, dvb.h:1173-1416)
+ * behind one object.  Every stream's tiles ride in the same launches; seam repair, the alignment decision (dvb.h:1402-1411) and
+ * every count stay on the device, and the host does nothing between run_async and wait (no synchronise, no readback, no launch that
+ * depends on data).  The number of launches of a run does not depend on n_streams.
+ * One call commits, per stream, a PREFIX of the stream's input: a whole number of 128-block chunks (dvb.h:1372-1373 decides how many
+ * fit into n_in and cap_out), for which the bytes written and the decoder state afterwards are the reference's.  The prefix is shorter
+ * than what fits only behind a resync chunk whose decision changed the alignment (`switched`: the rest belongs to the new alignment)
+ * or in front of a seam that still failed verification after the device's repair rounds (`stalled`).  A stream with at least one chunk
+ * available always commits at least one: continue with in + consumed, out + produced until consumed is 0.  The bytes do not depend on
+ * how a stream is cut into calls, nor on what the other streams of the batch hold. */
+typedef struct lsdr_viterbi_batch lsdr_viterbi_batch;
+typedef struct {
+  uint64_t consumed;        /* soft symbols of this call's input that are now decoded (whole chunks) */
+  uint64_t produced;        /* bytes written to the stream's out pointer */
+  uint32_t current_sync;    /* alignment in force after the call */
+  uint32_t resync_phase;
+  uint32_t switched;        /* 1: the prefix ends behind a resync chunk that changed the alignment (dvb.h:1402-1411) */
+  uint32_t stalled;         /* 1: the prefix ends in front of a seam that did not verify after the device's repair rounds */
+  uint32_t tiles, repaired; /* tiles planned for the stream; tiles the device decoded again */
+} lsdr_viterbi_batch_result;
+/* max_symbols: the most symbols one stream hands to one run (sizes the per-resync-chunk records).  Errors as lsdr_viterbi_create. */
+int lsdr_viterbi_batch_create(lsdr_ctx *ctx, int cstln, int rate, int n_streams, size_t max_symbols, lsdr_viterbi_batch **vb);
+void lsdr_viterbi_batch_destroy(lsdr_viterbi_batch *vb);
+int lsdr_viterbi_batch_set_resync_period(lsdr_viterbi_batch *vb, int period);   /* all streams; not while a run is in flight */
+/* stream i (all streams if i < 0) becomes a freshly constructed viterbi_sync; ordered on the context's stream; not while a run is in flight */
+int lsdr_viterbi_batch_reset(lsdr_viterbi_batch *vb, int i);
+/* in_dev / out_dev: HOST arrays of n_streams DEVICE pointers (out 4-byte aligned, else LSDR_E_ARG; in may be NULL where n_in is 0).
+ * n_in: HOST array, symbols available per stream (<= max_symbols).  n_in_dev: NULL, or a DEVICE array of n_streams uint64 counts written
+ * by earlier work on the context's stream; stream i then decodes min(n_in[i], n_in_dev[i]) symbols.  cap_out: bytes each out pointer can
+ * take.  Queues everything and returns at once; one run is in flight per object (a second run_async before wait: LSDR_E_ARG). */
+int lsdr_viterbi_batch_run_async(lsdr_viterbi_batch *vb, const lsdr_softsymbol *const *in_dev, const size_t *n_in,
+                                 const uint64_t *n_in_dev, uint8_t *const *out_dev, size_t cap_out);
+/* synchronises the context's stream once and copies n_streams records (results may be NULL) */
+int lsdr_viterbi_batch_wait(lsdr_viterbi_batch *vb, lsdr_viterbi_batch_result *results);
+/* the same records on the device ([n_streams], valid once the run's work on the stream is done), for a consumer kernel */
+const lsdr_viterbi_batch_result *lsdr_viterbi_batch_results_dev(const lsdr_viterbi_batch *vb);
+/* kernel launches queued by the last run_async; run_async calls since create */
+int lsdr_viterbi_batch_stats(const lsdr_viterbi_batch *vb, unsigned *launches_last_run, unsigned long long *runs);
+
 /* ---- mpeg_sync<u8,0>, dvb.h:712-891: bit alignment, polarity and 0x47/0xB8 sync search, lock tracking.
  * One run() call.  *call_next_sync = 1 when the reference would call deconv->next_sync() (dvb.h:771-779);
  * state_events (host, may be NULL) receives the values written to the lock-state pipe (0/1), at most 2.

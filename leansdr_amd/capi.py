@@ -232,6 +232,25 @@ _sig("lsdr_viterbi_stats", C.c_int, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint
 _sig("lsdr_viterbi_repair_stats", C.c_int, [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
 _sig("lsdr_viterbi_q4_supported", C.c_int, [C.c_int, C.c_int])
 _sig("lsdr_viterbi_run", C.c_int, [vp, vp, c_sz, vp, c_sz, psz, psz])
+
+
+class ViterbiBatchResult(C.Structure):
+    """lsdr_viterbi_batch_result"""
+    _fields_ = [("consumed", C.c_uint64), ("produced", C.c_uint64), ("current_sync", C.c_uint32), ("resync_phase", C.c_uint32),
+                ("switched", C.c_uint32), ("stalled", C.c_uint32), ("tiles", C.c_uint32), ("repaired", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+_sig("lsdr_viterbi_batch_create", C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_sz, C.POINTER(vp)])
+_sig("lsdr_viterbi_batch_destroy", None, [vp])
+_sig("lsdr_viterbi_batch_set_resync_period", C.c_int, [vp, C.c_int])
+_sig("lsdr_viterbi_batch_reset", C.c_int, [vp, C.c_int])
+_sig("lsdr_viterbi_batch_run_async", C.c_int, [vp, C.POINTER(vp), psz, vp, C.POINTER(vp), c_sz])
+_sig("lsdr_viterbi_batch_wait", C.c_int, [vp, C.POINTER(ViterbiBatchResult)])
+_sig("lsdr_viterbi_batch_results_dev", vp, [vp])
+_sig("lsdr_viterbi_batch_stats", C.c_int, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong)])
 _sig("lsdr_mpeg_sync_create", C.c_int, [vp, C.c_int, C.POINTER(vp)])
 _sig("lsdr_mpeg_sync_destroy", None, [vp])
 _sig("lsdr_mpeg_sync_locked", C.c_int, [vp])
@@ -1002,6 +1021,92 @@ class Viterbi:
         out = self.ctx.download(dout, np.uint8, nout)
         din.free(); dout.free()
         return out, pos
+
+
+class ViterbiBatch:
+    """n_streams independent viterbi_sync decoders (dvb.h:1173-1416) behind one object: every stream's tiles in the same launches,
+    seam repair, the alignment decision and all counts on the device (lsdr_viterbi_batch_*)."""
+
+    def __init__(self, ctx, cstln, rate, n_streams, max_symbols, resync_period=0):
+        self.ctx, self.n = ctx, int(n_streams)
+        h = vp()
+        check(lib.lsdr_viterbi_batch_create(ctx.h, cstln, rate, n_streams, max_symbols, C.byref(h)))
+        self.h = h
+        if resync_period:
+            check(lib.lsdr_viterbi_batch_set_resync_period(h, resync_period))
+
+    def close(self):
+        if self.h:
+            lib.lsdr_viterbi_batch_destroy(self.h)
+            self.h = None
+
+    def reset(self, i=-1):
+        check(lib.lsdr_viterbi_batch_reset(self.h, i))
+
+    def stats(self):
+        l, r = C.c_uint(), C.c_ulonglong()
+        check(lib.lsdr_viterbi_batch_stats(self.h, C.byref(l), C.byref(r)))
+        return dict(launches_last_run=l.value, runs=r.value)
+
+    @property
+    def results_dev(self):
+        return lib.lsdr_viterbi_batch_results_dev(self.h)
+
+    def run_async_dev(self, in_ptrs, n_in, out_ptrs, cap_out, n_in_dev=None):
+        """Queues one run.  in_ptrs / out_ptrs: device addresses per stream (int, c_void_p or None); n_in: symbols per stream;
+        n_in_dev: device address of n_streams uint64 counts, or None."""
+        def addr(p):
+            return p.value if isinstance(p, vp) else p
+        ins = (vp * self.n)(*[addr(p) for p in in_ptrs])
+        outs = (vp * self.n)(*[addr(p) for p in out_ptrs])
+        ns = (c_sz * self.n)(*[int(x) for x in n_in])
+        check(lib.lsdr_viterbi_batch_run_async(self.h, ins, ns, n_in_dev, outs, int(cap_out)))
+
+    def wait(self):
+        res = (ViterbiBatchResult * self.n)()
+        check(lib.lsdr_viterbi_batch_wait(self.h, res))
+        return [r.as_dict() for r in res]
+
+    def run_streams(self, syms, pipe=None, n_in_dev=None):
+        """Whole streams: uploads, then repeats run -> wait with every stream advanced by its own `consumed` until no stream makes
+        progress (a run stops a stream early behind an alignment switch or in front of a seam that did not verify).
+        pipe: at most that many symbols of a stream per run.  n_in_dev: per-stream symbol counts that reach the decoder through
+        device memory (written by a device copy queued just before every run, without a host synchronise): stream i ends there.
+        Returns ([(bytes, consumed_total, current_sync) per stream], runs)."""
+        assert len(syms) == self.n
+        syms = [np.ascontiguousarray(s, SOFTSYM) for s in syms]
+        cap = max(len(s) for s in syms) + 64
+        dins = [self.ctx.upload(s) if len(s) else None for s in syms]
+        douts = [self.ctx.alloc(cap) for _ in syms]
+        limit = [len(s) for s in syms] if n_in_dev is None else [min(len(s), int(m)) for s, m in zip(syms, n_in_dev)]
+        d_src = d_cnt = None
+        if n_in_dev is not None:
+            d_src, d_cnt = self.ctx.alloc(8 * self.n), self.ctx.alloc(8 * self.n)
+        pos, nout, cur, runs = [0] * self.n, [0] * self.n, [0] * self.n, 0
+        while True:
+            n_in = [len(s) - p if pipe is None else min(pipe, len(s) - p) for s, p in zip(syms, pos)]
+            cnt_ptr = None
+            if n_in_dev is not None:
+                left = np.array([max(l - p, 0) for l, p in zip(limit, pos)], np.uint64)
+                check(lib.lsdr_memcpy_h2d(self.ctx.h, d_src.ptr, _np(left), left.nbytes))
+                self.ctx.sync()
+                check(lib.lsdr_memcpy_d2d(self.ctx.h, d_cnt.ptr, d_src.ptr, left.nbytes))     # queued; the run reads it on the device
+                cnt_ptr = d_cnt.ptr
+            self.run_async_dev([d.at(p * 4) if d is not None else None for d, p in zip(dins, pos)], n_in,
+                               [d.at(o) for d, o in zip(douts, nout)], cap - max(nout), cnt_ptr)
+            res = self.wait()
+            runs += 1
+            for i, r in enumerate(res):
+                pos[i] += r["consumed"]
+                nout[i] += r["produced"]
+                cur[i] = r["current_sync"]
+            if not any(r["consumed"] for r in res):
+                break
+        out = [(self.ctx.download(d, np.uint8, n) if n else np.empty(0, np.uint8), p, c) for d, n, p, c in zip(douts, nout, pos, cur)]
+        for d in dins + douts + [d_src, d_cnt]:
+            if d is not None:
+                d.free()
+        return out, runs
 
 
 class MpegSync:

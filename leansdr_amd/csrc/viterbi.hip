@@ -72,6 +72,18 @@ struct vit_job {            // one wavefront's work
   int emit;                          // write decoded bytes
   unsigned chunk_step;               // distance between emitted chunks (1: contiguous; P: the resync chunks only)
   unsigned slot;                     // where the job's begin/end/first states and totals go (normally its own index)
+  unsigned stream;                   // batch (viterbi_batch.h): the stream the job belongs to, an index into vit_args::streams
+};
+
+// One stream of a batch (lsdr_viterbi_batch, viterbi_batch.h): what the single-stream launch passes by value in vit_args, read from
+// device memory once per job.
+struct vit_bstream {
+  const lsdr_softsymbol *in;
+  unsigned char *out;
+  const vit_state *states;           // the stream's carried decoder states [nsyncs]
+  unsigned long long chunks;         // chunks of this run: planned by the host from the lengths, clipped by k_vitb_prep to the device-side count
+  int phase0;                        // resync phase of the stream's chunk 0
+  unsigned rbase;                    // the stream's first row in r_totals / r_states
 };
 
 struct vit_args {
@@ -96,6 +108,14 @@ struct vit_args {
   // k_viterbi as the device-side repair round: only the jobs whose seam flag cond[slot] is set run, each from the end state of the slot
   // before its own (states_in = the slot array of end states), without warm-up; a job that starts a chain (from_state ≥ 0) has no seam
   const int *cond;
+  // BATCH kernels only.  Jobs take `in`, `out`, the carried states and the resync phase from streams[job.stream]; jobs beyond the stream's
+  // device-side chunk count leave at once, the one across it is clipped.  Totals and states go to one row per resync chunk of the stream
+  // ([row][nsyncs]: row = rbase + index of the resync chunk within the run) instead of the per-slot arrays: the decision kernel reads them
+  // without knowing the tiling.
+  const vit_bstream *streams;
+  int *r_totals;
+  vit_state *r_states;
+  int nsyncs;
 };
 
 // Minimum over the 64 lanes, returned wave-uniform: DPP steps inside the rows of 16 (quad swaps, half mirror, mirror), two
@@ -137,7 +157,7 @@ constexpr int kVitWaves = 4;
 // path's chain of table read → shuffle → compare → table read → shuffle (≈ 900 cycles per step).  Same candidates, same
 // order, same `<=` tie rule as the generic path: bit-identical.
 // NUS = 2 / 4: that fast path (4: 8PSK 2/3 — four predecessors, eight labels, twelve independent ds_bpermute); 0 = generic.
-template <int NUS>
+template <int NUS, bool BATCH = false>
 __global__ __launch_bounds__(kVitWaves * 64) void k_viterbi(vit_args a) {
   constexpr bool TWO = NUS == 2;
   // The generic path walks the trellis tables in its inner loop: they live in LDS (≈ 41 KB per workgroup — three workgroups,
@@ -155,9 +175,23 @@ __global__ __launch_bounds__(kVitWaves * 64) void k_viterbi(vit_args a) {
   const vit_tables &T = NUS == 0 ? *reinterpret_cast<const vit_tables *>(t_raw) : *a.T;
   if (jid >= a.njobs) return;
   vit_job job = a.jobs[jid];
+  const lsdr_softsymbol *in = a.in;
+  unsigned char *out = a.out;
+  const vit_state *states_in = a.states_in;
+  int phase0 = a.resync_phase0;
+  unsigned rrow = 0;                 // BATCH: row of resync chunk c is rrow + (c + phase0) / period (mod 2^32: rrow may be rbase − 1)
+  if (BATCH) {
+    const vit_bstream S = a.streams[job.stream];
+    if (job.first_chunk >= S.chunks) return;
+    const unsigned long long left = (S.chunks - job.first_chunk + job.chunk_step - 1) / job.chunk_step;
+    if (left < job.n_chunks) job.n_chunks = (unsigned)left;
+    in = S.in; out = S.out; states_in = S.states; phase0 = S.phase0;
+    rrow = S.rbase - (S.phase0 > 0 ? 1u : 0u);
+  }
   if (a.cond) {
     if (job.from_state >= 0 || !a.cond[job.slot]) return;
     job.warm = 0; job.from_state = (int)job.slot - 1;
+    if (BATCH) states_in = a.end_states;
   }
   const unsigned char *map = a.maps + job.sync * 256;
   const int shift = a.shifts[job.sync];
@@ -169,7 +203,7 @@ __global__ __launch_bounds__(kVitWaves * 64) void k_viterbi(vit_args a) {
 
   int cost;
   unsigned long long path;
-  if (job.from_state >= 0) { cost = a.states_in[job.from_state].cost[lane]; path = a.states_in[job.from_state].path[lane]; }
+  if (job.from_state >= 0) { cost = states_in[job.from_state].cost[lane]; path = states_in[job.from_state].path[lane]; }
   else { cost = 0; path = 0; }
   // TWO: per-lane constants of the trellis
   const int pred0 = T.pred[0][lane], pred1 = T.pred[1][lane];
@@ -189,13 +223,13 @@ __global__ __launch_bounds__(kVitWaves * 64) void k_viterbi(vit_args a) {
       a.begin_states[job.slot].cost[lane] = cost;
       a.begin_states[job.slot].path[lane] = path;
     }
-    const bool resync = ((c + (unsigned long long)a.resync_phase0) % (unsigned)a.resync_period) == 0;
+    const bool resync = ((c + (unsigned long long)phase0) % (unsigned)a.resync_period) == 0;
     const bool want_q = resync && emitting;
     int total = 0;
     unsigned long long outstream = 0;
     int nout = 0;
-    unsigned char *pout = a.out + c * (unsigned)(kChunkBlocks * C.bits_in / 8);
-    const lsdr_softsymbol *pin = a.in + c * (unsigned)(kChunkBlocks * a.nshifts) + shift;
+    unsigned char *pout = out + c * (unsigned)(kChunkBlocks * C.bits_in / 8);
+    const lsdr_softsymbol *pin = in + c * (unsigned)(kChunkBlocks * a.nshifts) + shift;
     // update_sync (dvb.h:1353-1364) for the whole chunk at once: lane l prepares FEC blocks l and l+64 (coded
     // symbol = mapped bits of the block's `nshifts` symbols, cost = their summed costs); the trellis loop below
     // then takes block b's pair with two v_readlane instead of dependent global loads on its critical path.
@@ -317,7 +351,13 @@ __global__ __launch_bounds__(kVitWaves * 64) void k_viterbi(vit_args a) {
     }
     // renormalise once per chunk (the reference subtracts the best metric after every step)
     cost -= wave_min(cost);
-    if (emitting) {
+    if (BATCH) {
+      if (want_q) {
+        const size_t row = (size_t)(rrow + (unsigned)((c + (unsigned long long)phase0) / (unsigned)a.resync_period)) * (unsigned)a.nsyncs + (unsigned)job.sync;
+        if (lane == 0) a.r_totals[row] = total;
+        a.r_states[row].cost[lane] = cost; a.r_states[row].path[lane] = path;
+      }
+    } else if (emitting) {
       const unsigned ci = (unsigned)q;
       if (lane == 0) a.totals[(size_t)job.slot * a.totals_stride + ci] = total;
       if (a.chunk_states) {
@@ -515,7 +555,7 @@ template <int NUS> __device__ __forceinline__ void store_state(const regs<NUS> &
 struct sym4 { unsigned v[4]; };
 }  // namespace q4
 
-template <int NUS>
+template <int NUS, bool BATCH = false>
 __global__ __launch_bounds__(64) void k_viterbi_q4(vit_args a) {
   using namespace q4;
   constexpr int BITS_IN = NUS == 2 ? 1 : 2;          // decoded bits per step
@@ -530,7 +570,22 @@ __global__ __launch_bounds__(64) void k_viterbi_q4(vit_args a) {
   else { jid = a.q4_n_main + (blockIdx.x - a.q4_main_waves) * 16u + quad; valid = jid < a.njobs; }
   vit_job job;
   if (valid) job = a.jobs[jid];
-  else { job.first_chunk = 0; job.n_chunks = 0; job.warm = 0; job.sync = 0; job.from_state = -1; job.emit = 0; job.chunk_step = 1; job.slot = 0; }
+  else { job.first_chunk = 0; job.n_chunks = 0; job.warm = 0; job.sync = 0; job.from_state = -1; job.emit = 0; job.chunk_step = 1; job.slot = 0; job.stream = 0; }
+  const lsdr_softsymbol *in = a.in;
+  unsigned char *out = a.out;
+  const vit_state *states_in = a.states_in;
+  int phase0 = a.resync_phase0;
+  unsigned rrow = 0;
+  if (BATCH) {
+    const vit_bstream S = a.streams[job.stream];
+    if (valid && job.first_chunk >= S.chunks) { valid = false; job.n_chunks = 0; job.warm = 0; }
+    if (valid) {
+      const unsigned long long left = (S.chunks - job.first_chunk + job.chunk_step - 1) / job.chunk_step;
+      if (left < job.n_chunks) job.n_chunks = (unsigned)left;
+    }
+    in = S.in; out = S.out; states_in = S.states; phase0 = S.phase0;
+    rrow = S.rbase - (S.phase0 > 0 ? 1u : 0u);
+  }
   const int wmax = -wave_min(-(int)job.warm), nmax = -wave_min(-(int)job.n_chunks);
   const unsigned char *map = a.maps + job.sync * 256;
   const unsigned map_lo = (unsigned)map[0] | ((unsigned)map[1] << 8) | ((unsigned)map[2] << 16) | ((unsigned)map[3] << 24);
@@ -549,7 +604,7 @@ __global__ __launch_bounds__(64) void k_viterbi_q4(vit_args a) {
   }
 
   regs<NUS> R;
-  if (valid && job.from_state >= 0) load_state<NUS>(R, a.states_in[job.from_state], q);
+  if (valid && job.from_state >= 0) load_state<NUS>(R, states_in[job.from_state], q);
   else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) { R.c[r] = 0; R.p[r] = 0; if constexpr (NUS == 4) R.ph[r] = 0; }
@@ -558,7 +613,7 @@ __global__ __launch_bounds__(64) void k_viterbi_q4(vit_args a) {
   // i of lane k of the quad)
   auto load_group = [&](long long qq, int g, sym4 &o) {
     const unsigned long long c = (unsigned long long)((long long)job.first_chunk + qq * (long long)job.chunk_step);
-    const unsigned *p = reinterpret_cast<const unsigned *>(a.in + c * (unsigned)kChunkBlocks + (unsigned)(16 * g + q));
+    const unsigned *p = reinterpret_cast<const unsigned *>(in + c * (unsigned)kChunkBlocks + (unsigned)(16 * g + q));
 #pragma unroll
     for (int i = 0; i < 4; ++i) o.v[i] = p[4 * i];
   };
@@ -571,11 +626,11 @@ __global__ __launch_bounds__(64) void k_viterbi_q4(vit_args a) {
     const unsigned long long c = (unsigned long long)((long long)job.first_chunk + (long long)qq * (long long)job.chunk_step);
     const bool emitting = qq >= 0;
     if (qq == 0) store_state<NUS>(R, a.begin_states[job.slot], q);
-    const bool resync = ((c + (unsigned long long)a.resync_phase0) % (unsigned)a.resync_period) == 0;
+    const bool resync = ((c + (unsigned long long)phase0) % (unsigned)a.resync_period) == 0;
     const bool want_q = resync && emitting, do_emit = emitting && job.emit;
     int total = 0;
     unsigned outw = 0;
-    unsigned *pout = reinterpret_cast<unsigned *>(a.out + c * (unsigned)(kChunkBlocks * BITS_IN / 8));
+    unsigned *pout = reinterpret_cast<unsigned *>(out + c * (unsigned)(kChunkBlocks * BITS_IN / 8));
 #pragma unroll 1
     for (int g = 0; g < 8; ++g) {
       // decode this group's symbols (update_sync, dvb.h:1353-1364, nshifts = 1), fetch the next group's
@@ -629,7 +684,13 @@ __global__ __launch_bounds__(64) void k_viterbi_q4(vit_args a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) R.c[r] -= m;
     }
-    if (emitting) {
+    if (BATCH) {
+      if (want_q) {
+        const size_t row = (size_t)(rrow + (unsigned)((c + (unsigned long long)phase0) / (unsigned)a.resync_period)) * (unsigned)a.nsyncs + (unsigned)job.sync;
+        if (q == 0) a.r_totals[row] = total;
+        store_state<NUS>(R, a.r_states[row], q);
+      }
+    } else if (emitting) {
       const unsigned ci = (unsigned)qq;
       if (q == 0) a.totals[(size_t)job.slot * a.totals_stride + ci] = total;
       if (a.chunk_states) store_state<NUS>(R, a.chunk_states[(size_t)job.slot * a.totals_stride + ci], q);
@@ -810,6 +871,7 @@ static int vit_launch(lsdr_viterbi *v, const lsdr_softsymbol *in, uint8_t *out, 
   a.njobs = (unsigned)up.size();
   a.q4_n_main = a.njobs; a.q4_main_waves = 0;
   a.cond = nullptr;
+  a.streams = nullptr; a.r_totals = nullptr; a.r_states = nullptr; a.nsyncs = v->nsyncs;
   if (args_out) *args_out = a;
   const dim3 grid((unsigned)((up.size() + kVitWaves - 1) / kVitWaves)), block(kVitWaves * 64);
   // (test hooks, read at every call so that one process can exercise every kernel)
@@ -1384,3 +1446,5 @@ static int viterbi_run_aligned(lsdr_viterbi *v, const lsdr_softsymbol *in, size_
 }
 
 }  // extern "C"
+
+#include "viterbi_batch.h"
