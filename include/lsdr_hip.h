@@ -676,7 +676,31 @@ int lsdr_drifter_run(lsdr_drifter *d, const lsdr_cf32 *in, size_t n, lsdr_cf32 *
  * anf ∈ {0, 1}; omega = Fs/Fm ∈ [1, 8]; tile_len a multiple of 2048 (0: 4096), tile_warmup a multiple of 128 (0: 512).
  * One batch in flight per object: run_async → wait → [ts_download_async → ts_wait]; the NEXT run_async may be queued while the
  * download is in flight (its last kernel waits for it).  Use two objects on two contexts to overlap one batch's tail with the other's
- * front end. */
+ * front end.
+ *
+ * The VITERBI engine (lsdr_capture_batch_create_viterbi) is the same object for `leandvb --u8 … --viterbi` (leandvb.cc:498-501, 532-540,
+ * 558-596), the graph that decodes weak signals:
+ *     cconverter<u8> → auto_notch → cstln_receiver(linear_sampler, QPSK, pll_adjustment / 6) → viterbi_sync → mpeg_sync(deconv = NULL) →
+ *     deinterleaver → rs_decoder → derandomizer
+ *  * front end: the same tiles with SOFT symbols out — per symbol one lsdr_softsymbol, `symbol` the two sign bits, `cost` the exact integer
+ *    arithmetic of the constellation table on the tile's truncated coordinates; so cost and symbol are exact functions of the tile's own
+ *    sampled point and only the loop trajectory is tolerance-class, as in the default engine (tile 0 is the reference's arithmetic).  A
+ *    cost scales with the point's amplitude, and a tile cannot reproduce the serial AGC (an average over a hundred chunks) in its warm-up:
+ *    the record's coordinates are taken at the gain of a second power estimator that the tile starts from the mean it measured over its
+ *    warm-up, while timing and carrier loops run exactly as in the default engine (leansdr_amd/csrc/rxb_device.h).  The
+ *    records are staged transposed (row = symbol step, column = tile: a wavefront's 64 tiles write 64 consecutive dwords) and compacted
+ *    into one contiguous array per capture, its count in device memory.  Memory: 4 bytes per symbol, staged and compacted — about 7 bytes
+ *    per input sample at 1.2 samples per symbol (the default engine: about 0.5).
+ *  * Viterbi stage: one lsdr_viterbi_batch, a stream per capture, on the context the tail runs on; it reads the compacted soft symbols
+ *    with their counts from device memory and writes straight into the tail's byte buffers.  lsdr_viterbi_batch commits a prefix per
+ *    call and plans the next call on the host, so a batch takes several ROUNDS.  run_async queues the front end and round 1; WAIT DRIVES
+ *    THE REMAINING ROUNDS (one host read of B records per round, every round shared by all captures: their number does not grow with B),
+ *    then queues the tail and waits for it.  The bytes are viterbi_sync's whatever the number of rounds.
+ *  * FEC tail: mpeg_sync's search runs over bytes that are already there (no deconvol_sync, no next_sync()); the rest is the same.  In the
+ *    result, bytes_deconv is the number of bytes viterbi_sync committed, next_sync_calls is 0, alignment is viterbi_sync's current_sync.
+ * cfg->fec is viterbi_sync's code rate, with leandvb's rule "QPSK 2/3 is handled as 4/6"; what lsdr_viterbi_batch_create refuses is
+ * refused here with the same code.  Every other call works on both kinds of object; words_dev returns NULL on a Viterbi object, soft_dev
+ * and viterbi_stats NULL / LSDR_E_ARG on a default one.  The accessors return NULL for i outside [0, n_captures). */
 typedef struct lsdr_capture_batch lsdr_capture_batch;
 typedef struct {
   int n_captures;            /* B */
@@ -706,7 +730,22 @@ typedef struct {
   uint32_t next_sync_calls, locked, alignment, bitphase;     /* deconvol_sync::next_sync() calls; mpeg_sync locked at the end; alignment in force */
   uint32_t tiles, seam_dup, seam_miss, seam_bad;             /* receiver seams: duplicates dropped, symbols re-inserted, unreconciled */
 } lsdr_capture_result;
+typedef struct {
+  int resync_period;         /* viterbi_sync::resync_period in chunks (0: 32, dvb.h:1232) */
+  int reserved[7];           /* 0 */
+} lsdr_capture_viterbi_cfg;
+typedef struct {             /* the Viterbi stage of capture i in the last batch */
+  uint32_t rounds;           /* lsdr_viterbi_batch calls in which this capture's stream committed symbols */
+  uint32_t batch_rounds;     /* calls the batch made (the last one finds nothing left to commit in any stream) */
+  uint32_t switches, stalls; /* calls that ended behind an alignment switch / in front of an unverified seam */
+  uint32_t tiles, repaired;  /* Viterbi tiles planned; tiles the device decoded again */
+  uint32_t current_sync, pad;
+  uint64_t symbols, bytes;   /* soft symbols consumed, bytes committed */
+} lsdr_capture_viterbi_stats;
 int lsdr_capture_batch_create(lsdr_ctx *ctx, const lsdr_capture_batch_cfg *cfg, lsdr_capture_batch **b);
+/* vcfg may be NULL (defaults) */
+int lsdr_capture_batch_create_viterbi(lsdr_ctx *ctx, const lsdr_capture_batch_cfg *cfg, const lsdr_capture_viterbi_cfg *vcfg,
+                                      lsdr_capture_batch **b);
 void lsdr_capture_batch_destroy(lsdr_capture_batch *b);
 /* iq_dev: HOST array of B DEVICE pointers to lsdr_cu8 items (16-byte aligned), n_samples each.  Queues everything; returns at once. */
 int lsdr_capture_batch_run_async(lsdr_capture_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples);
@@ -719,6 +758,9 @@ const uint8_t *lsdr_capture_batch_ts_dev(const lsdr_capture_batch *b, int i);   
 const uint32_t *lsdr_capture_batch_words_dev(const lsdr_capture_batch *b, int i);     /* its packed decisions (16 per word, MSB first) */
 const uint8_t *lsdr_capture_batch_bytes_dev(const lsdr_capture_batch *b, int i);      /* deconvol_sync's output, mpeg_sync's output */
 const uint8_t *lsdr_capture_batch_mpeg_dev(const lsdr_capture_batch *b, int i);
+/* Viterbi objects: capture i's compacted soft symbols (result.symbols of them), the Viterbi stage's counters after wait */
+const lsdr_softsymbol *lsdr_capture_batch_soft_dev(const lsdr_capture_batch *b, int i);
+int lsdr_capture_batch_viterbi_stats(const lsdr_capture_batch *b, int i, lsdr_capture_viterbi_stats *stats);
 /* the notch's detected bins of capture i after a run (tests): bins[0 … *n) */
 int lsdr_capture_batch_bins(lsdr_capture_batch *b, int i, int *bins, unsigned cap, unsigned *n);
 /* tests: the NOTCHED stream of capture i exactly as the tiles of the last run saw it — the same start state per tile (from the estimator

@@ -302,7 +302,23 @@ class CaptureResult(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class CaptureViterbiCfg(C.Structure):
+    _fields_ = [("resync_period", C.c_int), ("reserved", C.c_int * 7)]
+
+
+class CaptureViterbiStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("batch_rounds", C.c_uint32), ("switches", C.c_uint32), ("stalls", C.c_uint32),
+                ("tiles", C.c_uint32), ("repaired", C.c_uint32), ("current_sync", C.c_uint32), ("pad", C.c_uint32),
+                ("symbols", C.c_uint64), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
 _sig("lsdr_capture_batch_create", C.c_int, [vp, C.POINTER(CaptureBatchCfg), C.POINTER(vp)])
+_sig("lsdr_capture_batch_create_viterbi", C.c_int, [vp, C.POINTER(CaptureBatchCfg), C.POINTER(CaptureViterbiCfg), C.POINTER(vp)])
+_sig("lsdr_capture_batch_soft_dev", vp, [vp, C.c_int])
+_sig("lsdr_capture_batch_viterbi_stats", C.c_int, [vp, C.c_int, C.POINTER(CaptureViterbiStats)])
 _sig("lsdr_capture_batch_destroy", None, [vp])
 _sig("lsdr_capture_batch_run_async", C.c_int, [vp, vp, c_sz])
 _sig("lsdr_capture_batch_wait", C.c_int, [vp, vp])
@@ -807,10 +823,11 @@ class RxBatch:
 
 class CaptureBatch:
     """lsdr_capture_batch: B independent cu8 captures, each from its first sample to TS (leandvb's default `--u8` graph per capture),
-    in shared launches with the counts on the device."""
+    in shared launches with the counts on the device.  viterbi=True (or a dict of lsdr_capture_viterbi_cfg fields): the `--viterbi` graph —
+    soft symbols, viterbi_sync, mpeg_sync without a deconvolver."""
 
     def __init__(self, ctx, n_captures, max_samples, omega, fec=FEC12, anf=1, tile_len=0, tile_warmup=0, notch_k=0.0, notch_decimation=0,
-                 unlocked_window=0, aux_cus=0):
+                 unlocked_window=0, aux_cus=0, viterbi=None):
         self.ctx, self.n = ctx, int(n_captures)
         cfg = CaptureBatchCfg()
         cfg.n_captures, cfg.max_samples, cfg.omega, cfg.fec, cfg.anf = self.n, int(max_samples), omega, fec, anf
@@ -819,7 +836,13 @@ class CaptureBatch:
         cfg.aux_cus = aux_cus
         self.unlocked_window = unlocked_window or 8192
         h = vp()
-        check(lib.lsdr_capture_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.viterbi = bool(viterbi)
+        if self.viterbi:
+            vcfg = CaptureViterbiCfg()
+            vcfg.resync_period = int(viterbi.get("resync_period", 0)) if isinstance(viterbi, dict) else 0
+            check(lib.lsdr_capture_batch_create_viterbi(ctx.h, C.byref(cfg), C.byref(vcfg), C.byref(h)))
+        else:
+            check(lib.lsdr_capture_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
         self.h = h
         self._res = (CaptureResult * self.n)()
 
@@ -865,6 +888,26 @@ class CaptureBatch:
             check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(w), lib.lsdr_capture_batch_words_dev(self.h, i), nw * 4))
             self.ctx.sync()
         return hs2_unpack(w, int(nsym))
+
+    def soft_ptr(self, i):
+        """Device pointer of capture i's compacted soft symbols (Viterbi objects; None otherwise or for i out of range)."""
+        return lib.lsdr_capture_batch_soft_dev(self.h, int(i))
+
+    def soft(self, i, n):
+        """The first n soft symbols of capture i after a run (Viterbi objects), as a SOFTSYM array (host)."""
+        a = np.empty(int(n), SOFTSYM)
+        p = self.soft_ptr(i)
+        if p is None:
+            raise LsdrError("capture batch: no soft symbols (not a Viterbi object, or no such capture)")
+        if n:
+            check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(a), p, int(n) * 4))
+            self.ctx.sync()
+        return a
+
+    def viterbi_stats(self, i):
+        st = CaptureViterbiStats()
+        check(lib.lsdr_capture_batch_viterbi_stats(self.h, int(i), C.byref(st)))
+        return st.as_dict()
 
     def stage_bytes(self, i, which, n):
         fn = lib.lsdr_capture_batch_bytes_dev if which == "deconv" else lib.lsdr_capture_batch_mpeg_dev

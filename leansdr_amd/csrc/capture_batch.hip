@@ -3,6 +3,12 @@
 // (rxb_device.h / rxb_host.h), the FEC tail fec.hip's lsdr_tail (tail_device.h / tail_host.h).
 //
 // Replaces, per capture, one `leandvb --u8 -f Fs --sr Fm --cr R` process of the reference (leandvb.cc:157-600: its default graph).
+//
+// The VITERBI engine (lsdr_capture_batch_create_viterbi) is `leandvb --u8 … --viterbi`: the front end writes soft symbols, one
+// lsdr_viterbi_batch (a stream per capture) decodes them straight into the tail's byte buffers, and the tail runs without deconvol_sync.
+// lsdr_viterbi_batch commits a prefix per call, so a batch takes several ROUNDS: run_async queues the front end and round 1 (symbol counts
+// from device memory), wait drives the remaining rounds — one host read of B records each, every round shared by all captures — and then
+// queues the tail.
 #include "lsdr_internal.h"
 
 struct lsdr_capture_batch {
@@ -17,7 +23,30 @@ struct lsdr_capture_batch {
   bool in_flight, dl_pending, waited;
   size_t consumed;
   std::vector<unsigned long long> n_ts;
+  // the Viterbi engine (vb != null)
+  lsdr_viterbi_batch *vb;
+  size_t soft_cap, byte_cap;
+  std::vector<lsdr_capture_viterbi_stats> vstats;
 };
+
+// one more round of the Viterbi stage: stream i continues behind what it has committed.  first: the symbol counts are still on the device.
+static int capture_batch_viterbi_round(lsdr_capture_batch *b, bool first, const std::vector<unsigned long long> &total,
+                                       const std::vector<unsigned long long> &done, const std::vector<unsigned long long> &bytes) {
+  const int n = b->cfg.n_captures;
+  std::vector<const lsdr_softsymbol *> in(n);
+  std::vector<uint8_t *> out(n);
+  std::vector<size_t> n_in(n);
+  unsigned long long most = 0;
+  for (int i = 0; i < n; ++i) {
+    in[i] = lsdr_rxb_soft(b->rx, (unsigned)i) + done[i];
+    out[i] = const_cast<uint8_t *>(lsdr_tail_bytes_dev(b->tail, (unsigned)i)) + bytes[i];
+    n_in[i] = (size_t)(first ? b->soft_cap : total[i] - done[i]);
+    if (bytes[i] > most) most = bytes[i];
+  }
+  return lsdr_viterbi_batch_run_async(b->vb, in.data(), n_in.data(), first ? reinterpret_cast<const uint64_t *>(lsdr_rxb_counts_dev(b->rx)) : nullptr,
+                                      out.data(), b->byte_cap - (size_t)most);
+}
+
 
 extern "C" {
 
@@ -26,6 +55,7 @@ void lsdr_capture_batch_destroy(lsdr_capture_batch *b) {
   if (b->dl) { (void)hipStreamSynchronize(b->dl); }
   if (b->ctx) (void)hipStreamSynchronize(b->ctx->stream);
   if (b->ctx_aux) (void)hipStreamSynchronize(b->ctx_aux->stream);
+  lsdr_viterbi_batch_destroy(b->vb);
   lsdr_tail_destroy(b->tail);
   lsdr_rxb_destroy(b->rx);
   if (b->ctx_aux) lsdr_ctx_destroy(b->ctx_aux);
@@ -50,18 +80,45 @@ static int capture_batch_partition(lsdr_capture_batch *b, lsdr_ctx *caller) {
   return LSDR_OK;
 }
 
-static int capture_batch_build(lsdr_capture_batch *b) {
+static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi_cfg *vcfg) {
   LSDR_HIP(hipSetDevice(b->ctx->device));
+  lsdr_ctx *const caller = b->ctx;
+  int vrate = b->cfg.fec;
+  if (vcfg) {
+    // what viterbi_sync cannot decode is refused before anything is allocated, with lsdr_viterbi_batch_create's own code
+    if (vrate == LSDR_FEC23) vrate = LSDR_FEC46;                        // "QPSK 2/3 is handled as 4/6", leandvb.cc:533-537
+    LSDR_ARG(vcfg->resync_period >= 0);
+    lsdr_viterbi_batch *probe = nullptr;
+    LSDR_TRY(lsdr_viterbi_batch_create(caller, LSDR_QPSK, vrate, 1, 4096, &probe));
+    lsdr_viterbi_batch_destroy(probe);
+  }
   if (b->cfg.aux_cus) LSDR_TRY(capture_batch_partition(b, b->ctx));
   lsdr_ctx *c = b->ctx;
-  LSDR_TRY(lsdr_rxb_create(c, &b->cfg, &b->rx));
-  const size_t sym_cap = lsdr_rxb_words_cap(b->rx) * 16;
-  LSDR_TRY(lsdr_tail_create(b->ctx_aux ? b->ctx_aux : c, (unsigned)b->cfg.n_captures, sym_cap, b->cfg.fec, b->cfg.unlocked_window ? b->cfg.unlocked_window : 8192u, &b->tail));
-  std::vector<const uint32_t *> words(b->cfg.n_captures);
-  for (int i = 0; i < b->cfg.n_captures; ++i) words[i] = lsdr_rxb_words(b->rx, (unsigned)i);
+  lsdr_ctx *const ct = b->ctx_aux ? b->ctx_aux : c;                     // the context the tail (and the Viterbi stage) runs on
+  const unsigned window = b->cfg.unlocked_window ? b->cfg.unlocked_window : 8192u;
   size_t stride = 0;
-  const void *counts = lsdr_rxb_results_dev(b->rx, &stride);
-  LSDR_TRY(lsdr_tail_bind(b->tail, words.data(), counts, stride));
+  if (vcfg) {
+    LSDR_TRY(lsdr_rxb_create_ex(c, &b->cfg, 1, 1.0f / 6.0f, &b->rx));   // cstln_receiver::pll_adjustment behind viterbi_sync, leandvb.cc:498-501
+    b->soft_cap = lsdr_rxb_soft_cap(b->rx);
+    LSDR_TRY(lsdr_viterbi_batch_create(ct, LSDR_QPSK, vrate, b->cfg.n_captures, b->soft_cap, &b->vb));
+    if (vcfg->resync_period > 0) LSDR_TRY(lsdr_viterbi_batch_set_resync_period(b->vb, vcfg->resync_period));
+    // viterbi_sync writes less than two bits per QPSK symbol at any rate
+    LSDR_TRY(lsdr_tail_create_ex(ct, (unsigned)b->cfg.n_captures, b->soft_cap, b->cfg.fec, window, 1, b->soft_cap / 4 + 64, &b->tail));
+    b->byte_cap = lsdr_tail_byte_cap(b->tail);
+    const void *counts = lsdr_rxb_results_dev(b->rx, &stride);
+    LSDR_TRY(lsdr_tail_bind(b->tail, nullptr, counts, stride));
+    lsdr_capture_viterbi_stats z;
+    memset(&z, 0, sizeof(z));
+    b->vstats.assign(b->cfg.n_captures, z);
+  } else {
+    LSDR_TRY(lsdr_rxb_create(c, &b->cfg, &b->rx));
+    const size_t sym_cap = lsdr_rxb_words_cap(b->rx) * 16;
+    LSDR_TRY(lsdr_tail_create(ct, (unsigned)b->cfg.n_captures, sym_cap, b->cfg.fec, window, &b->tail));
+    std::vector<const uint32_t *> words(b->cfg.n_captures);
+    for (int i = 0; i < b->cfg.n_captures; ++i) words[i] = lsdr_rxb_words(b->rx, (unsigned)i);
+    const void *counts = lsdr_rxb_results_dev(b->rx, &stride);
+    LSDR_TRY(lsdr_tail_bind(b->tail, words.data(), counts, stride));
+  }
   LSDR_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
   LSDR_HIP(hipEventCreateWithFlags(&b->ev_dl, hipEventDisableTiming));
   LSDR_HIP(hipStreamCreateWithFlags(&b->dl, hipStreamNonBlocking));
@@ -73,7 +130,20 @@ int lsdr_capture_batch_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, ls
   LSDR_ARG(c && cfg && out);
   lsdr_capture_batch *b = new lsdr_capture_batch();
   b->ctx = c; b->cfg = *cfg;
-  const int rc = capture_batch_build(b);
+  const int rc = capture_batch_build(b, nullptr);
+  if (rc) { lsdr_capture_batch_destroy(b); return rc; }
+  *out = b;
+  return LSDR_OK;
+}
+
+int lsdr_capture_batch_create_viterbi(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, const lsdr_capture_viterbi_cfg *vcfg, lsdr_capture_batch **out) {
+  LSDR_ARG(c && cfg && out);
+  lsdr_capture_viterbi_cfg v;
+  memset(&v, 0, sizeof(v));
+  if (vcfg) v = *vcfg;
+  lsdr_capture_batch *b = new lsdr_capture_batch();
+  b->ctx = c; b->cfg = *cfg;
+  const int rc = capture_batch_build(b, &v);
   if (rc) { lsdr_capture_batch_destroy(b); return rc; }
   *out = b;
   return LSDR_OK;
@@ -82,7 +152,14 @@ int lsdr_capture_batch_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, ls
 int lsdr_capture_batch_run_async(lsdr_capture_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples) {
   LSDR_ARG(b && iq_dev);
   if (b->in_flight) { lsdr_set_error("capture_batch: a batch is in flight (lsdr_capture_batch_wait first)"); return LSDR_E_ARG; }
+  if (b->vb) LSDR_TRY(lsdr_viterbi_batch_reset(b->vb, -1));              // every capture: a freshly constructed viterbi_sync
   LSDR_TRY(lsdr_rxb_launch(b->rx, reinterpret_cast<const void *const *>(iq_dev), n_samples, &b->consumed, b->ctx_aux ? b->ctx_aux->stream : nullptr));
+  if (b->vb) {
+    const std::vector<unsigned long long> zero(b->cfg.n_captures, 0ull);
+    LSDR_TRY(capture_batch_viterbi_round(b, true, zero, zero, zero));
+    b->in_flight = true; b->waited = false;
+    return LSDR_OK;
+  }
   LSDR_TRY(lsdr_tail_launch(b->tail, b->dl_pending ? b->ev_dl : nullptr));
   LSDR_HIP(hipEventRecord(b->ev_done, (b->ctx_aux ? b->ctx_aux : b->ctx)->stream));
   b->in_flight = true; b->waited = false;
@@ -92,6 +169,34 @@ int lsdr_capture_batch_run_async(lsdr_capture_batch *b, const lsdr_cu8 *const *i
 int lsdr_capture_batch_wait(lsdr_capture_batch *b, lsdr_capture_result *results) {
   LSDR_ARG(b);
   if (!b->in_flight) { lsdr_set_error("capture_batch: no batch in flight"); return LSDR_E_ARG; }
+  if (b->vb) {
+    // the remaining rounds of the Viterbi stage, then the tail
+    const int n = b->cfg.n_captures;
+    std::vector<lsdr_viterbi_batch_result> vr(n);
+    std::vector<unsigned long long> total(n, 0ull), done(n, 0ull), bytes(n, 0ull);
+    std::vector<unsigned> align(n, 0u);
+    lsdr_capture_viterbi_stats z;
+    memset(&z, 0, sizeof(z));
+    b->vstats.assign(n, z);
+    b->in_flight = false;                                               // (an error below leaves the object idle)
+    for (unsigned round = 1;; ++round) {
+      LSDR_TRY(lsdr_viterbi_batch_wait(b->vb, vr.data()));               // synchronises the stream: the front end's totals are on the host now
+      bool moved = false;
+      for (int i = 0; i < n; ++i) {
+        if (round == 1) LSDR_TRY(lsdr_rxb_seam_stats(b->rx, (unsigned)i, &total[i], nullptr, nullptr, nullptr));
+        lsdr_capture_viterbi_stats &s = b->vstats[i];
+        done[i] += vr[i].consumed; bytes[i] += vr[i].produced; align[i] = vr[i].current_sync;
+        if (vr[i].consumed) { moved = true; ++s.rounds; s.tiles += vr[i].tiles; s.repaired += vr[i].repaired; }
+        s.switches += vr[i].switched; s.stalls += vr[i].stalled;
+        s.batch_rounds = round; s.symbols = done[i]; s.bytes = bytes[i]; s.current_sync = align[i];
+      }
+      if (!moved) break;
+      LSDR_TRY(capture_batch_viterbi_round(b, false, total, done, bytes));
+    }
+    LSDR_TRY(lsdr_tail_set_bytes(b->tail, bytes.data(), align.data()));
+    LSDR_TRY(lsdr_tail_launch(b->tail, b->dl_pending ? b->ev_dl : nullptr));
+    LSDR_HIP(hipEventRecord(b->ev_done, (b->ctx_aux ? b->ctx_aux : b->ctx)->stream));
+  }
   LSDR_HIP(hipEventSynchronize(b->ev_done));
   b->in_flight = false; b->waited = true;
   const lsdr_tail_result *tr = lsdr_tail_results(b->tail);
@@ -131,10 +236,19 @@ int lsdr_capture_batch_ts_wait(lsdr_capture_batch *b) {
   return LSDR_OK;
 }
 
-const uint8_t *lsdr_capture_batch_ts_dev(const lsdr_capture_batch *b, int i) { return b && i >= 0 ? lsdr_tail_ts_dev(b->tail, (unsigned)i) : nullptr; }
-const uint32_t *lsdr_capture_batch_words_dev(const lsdr_capture_batch *b, int i) { return b && i >= 0 ? lsdr_rxb_words(b->rx, (unsigned)i) : nullptr; }
-const uint8_t *lsdr_capture_batch_bytes_dev(const lsdr_capture_batch *b, int i) { return b && i >= 0 ? lsdr_tail_bytes_dev(b->tail, (unsigned)i) : nullptr; }
-const uint8_t *lsdr_capture_batch_mpeg_dev(const lsdr_capture_batch *b, int i) { return b && i >= 0 ? lsdr_tail_mpeg_dev(b->tail, (unsigned)i) : nullptr; }
+static bool capture_index_ok(const lsdr_capture_batch *b, int i) { return b && i >= 0 && i < b->cfg.n_captures; }
+const uint8_t *lsdr_capture_batch_ts_dev(const lsdr_capture_batch *b, int i) { return capture_index_ok(b, i) ? lsdr_tail_ts_dev(b->tail, (unsigned)i) : nullptr; }
+const uint32_t *lsdr_capture_batch_words_dev(const lsdr_capture_batch *b, int i) { return capture_index_ok(b, i) ? lsdr_rxb_words(b->rx, (unsigned)i) : nullptr; }
+const uint8_t *lsdr_capture_batch_bytes_dev(const lsdr_capture_batch *b, int i) { return capture_index_ok(b, i) ? lsdr_tail_bytes_dev(b->tail, (unsigned)i) : nullptr; }
+const uint8_t *lsdr_capture_batch_mpeg_dev(const lsdr_capture_batch *b, int i) { return capture_index_ok(b, i) ? lsdr_tail_mpeg_dev(b->tail, (unsigned)i) : nullptr; }
+const lsdr_softsymbol *lsdr_capture_batch_soft_dev(const lsdr_capture_batch *b, int i) { return capture_index_ok(b, i) ? lsdr_rxb_soft(b->rx, (unsigned)i) : nullptr; }
+
+int lsdr_capture_batch_viterbi_stats(const lsdr_capture_batch *b, int i, lsdr_capture_viterbi_stats *out) {
+  LSDR_ARG(b && out && i >= 0 && i < b->cfg.n_captures);
+  if (!b->vb) { lsdr_set_error("capture_batch: not a Viterbi object (lsdr_capture_batch_create_viterbi)"); return LSDR_E_ARG; }
+  *out = b->vstats[i];
+  return LSDR_OK;
+}
 
 int lsdr_capture_batch_bins(lsdr_capture_batch *b, int i, int *bins, unsigned cap, unsigned *n) {
   LSDR_ARG(b && i >= 0 && i < b->cfg.n_captures);

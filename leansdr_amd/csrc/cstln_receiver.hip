@@ -609,7 +609,9 @@ __device__ __forceinline__ void rx_tile_meas(const rx_tiled_args &a, unsigned lo
 }
 
 // Tile 0: continues exactly from the carried state (one lane, the reference's arithmetic, exact table look-ups).
-template <int SAMP, int FMT, bool HARD>
+// SOFT_T (with HARD, the capture batch's soft tiles: rxb_device.h): the packed tails for the seam vote as with HARD, but the body as whole
+// soft symbols in the transposed layout, symbol k at a.stage[k·a.hpitch].
+template <int SAMP, int FMT, bool HARD, bool SOFT_T = false>
 __device__ __forceinline__ void rx_tile_exact(const rx_tiled_args &a) {
   const typename in_stream<FMT>::type src = in_make<FMT>(a.in);
   unsigned long long c1 = a.first_chunks;
@@ -624,7 +626,8 @@ __device__ __forceinline__ void rx_tile_exact(const rx_tiled_args &a) {
   auto emit = [&](lsdr_softsymbol ss) {
     if (HARD) {
       hacc = (hacc << 2) | (ss.symbol & 3u); htail = (htail << 2) | (ss.symbol & 3u);
-      if ((++cnt & 15u) == 0) a.hstage[(unsigned long long)((cnt >> 4) - 1) * a.hpitch] = hacc;
+      if (SOFT_T) { po[(unsigned long long)cnt * a.hpitch] = ss; ++cnt; }
+      else if ((++cnt & 15u) == 0) a.hstage[(unsigned long long)((cnt >> 4) - 1) * a.hpitch] = hacc;
     } else {
       po[cnt++] = ss;
     }
@@ -654,7 +657,7 @@ __device__ __forceinline__ void rx_tile_exact(const rx_tiled_args &a) {
   }
   ti.mu_end = s.mu; ti.phase_end = s.phase; ti.count = cnt;
   if (HARD) {
-    if (cnt & 15u) a.hstage[(unsigned long long)(cnt >> 4) * a.hpitch] = hacc << (2 * (16 - (cnt & 15u)));
+    if (!SOFT_T && (cnt & 15u)) a.hstage[(unsigned long long)(cnt >> 4) * a.hpitch] = hacc << (2 * (16 - (cnt & 15u)));
     rx_tile_info_h th;
     th.mu_begin = ti.mu_begin; th.phase_begin = ti.phase_begin; th.mu_end = ti.mu_end; th.phase_end = ti.phase_end;
     th.count = cnt; th.has_pre = 0; th.n_warm = 0; th.warm_tail = 0; th.body_tail = htail;

@@ -93,10 +93,14 @@ int lsdr_fir_stream_iv_launch(lsdr_ctx *c, const void *in, size_t n_in, lsdr_cf3
 // cstln_receiver.hip (rxb_host.h): the front end — auto_notch + cstln_receiver of every capture in shared launches, packed decisions out
 struct lsdr_rxb;
 int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **out);
+int lsdr_rxb_create_ex(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, lsdr_rxb **out);
 void lsdr_rxb_destroy(lsdr_rxb *b);
 int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t *consumed, hipStream_t aux = nullptr);
 const uint32_t *lsdr_rxb_words(const lsdr_rxb *b, unsigned i);
 size_t lsdr_rxb_words_cap(const lsdr_rxb *b);
+const lsdr_softsymbol *lsdr_rxb_soft(const lsdr_rxb *b, unsigned i);
+size_t lsdr_rxb_soft_cap(const lsdr_rxb *b);
+const unsigned long long *lsdr_rxb_counts_dev(const lsdr_rxb *b);
 const void *lsdr_rxb_results_dev(const lsdr_rxb *b, size_t *stride);
 unsigned lsdr_rxb_tiles(const lsdr_rxb *b);
 unsigned lsdr_rxb_detects(const lsdr_rxb *b);
@@ -112,6 +116,9 @@ struct lsdr_tail_result {          // = tail_device.h's tail_result
   unsigned long long first_lock_byte;
 };
 int lsdr_tail_create(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, lsdr_tail **out);
+int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, int nodeconv, size_t bytes_per_capture, lsdr_tail **out);
+int lsdr_tail_set_bytes(lsdr_tail *t, const unsigned long long *bytes, const unsigned *alignment);
+size_t lsdr_tail_byte_cap(const lsdr_tail *t);
 void lsdr_tail_destroy(lsdr_tail *t);
 int lsdr_tail_bind(lsdr_tail *t, const uint32_t *const *words, const void *counts_dev, size_t count_stride);
 int lsdr_tail_launch(lsdr_tail *t, hipEvent_t before_ts);

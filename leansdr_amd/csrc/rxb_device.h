@@ -11,6 +11,9 @@
 //   k_rxb_tiles<NOTCH>   the tolerance tiles (one lane per tile, 64 consecutive tiles of one capture per wavefront, cu8 samples staged
 //                        through LDS by buffer→LDS loads), packed 2-bit decisions out (rx_tiling.h "hs2")
 //   k_rxb_seam / k_rxb_compact   rx_tiling.h's seam pass and packed compaction, blockIdx.y = capture
+//   k_rxb_tiles_soft<NOTCH> / k_rxb_compact_soft   the same tiles with SOFT symbols out (leandvb --viterbi: viterbi_sync reads
+//                        softsymbol{cost, symbol}, sdr.h:287-290): one 4-byte record per body symbol, staged transposed (row = symbol
+//                        index, column = tile) and compacted through LDS into one contiguous lsdr_softsymbol array per capture
 //
 // The notch inside a tile.  sdr.h:119-138 with one slot is, per detect interval, estim[n] = (1−k)·estim[n−1] + k·x[n]·conj(e[n]),
 // out[n] = x[n] − estim[n]·e[n], e[n] = exp(j2π·bin·n/4096) (n counted from the block start; 4096·bin/4096 is whole, so the phasor runs
@@ -47,6 +50,11 @@ struct rxb_cap {
   float2 *T;                           // [n_pre] zero-start block sums of S
   int *cand;                           // [n_det][kDetMaxSlots]
   float2 *halves;                      // [n_det][2][2048]
+  // soft tiles only (null otherwise)
+  unsigned *sstage;                    // body symbol k of tile j at sstage[k·hpitch + j]: cost in bits 15:0, symbol in bits 23:16 (lsdr_softsymbol)
+  unsigned *spre;                      // [n_tiles] the warm-up's last symbol, as a soft record (the one a seam may re-insert)
+  unsigned *out_soft;                  // the capture's compacted soft symbols
+  unsigned long long *count_out;       // → the capture's entry of a contiguous uint64[n_captures]: symbols in out_soft
 };
 
 struct rxb_args {
@@ -223,6 +231,18 @@ __global__ __launch_bounds__(64) void k_rxb_notch_dump(rxb_args A, unsigned cap_
   }
 }
 
+// The table's cost for the truncated coordinates (qpsk_decide's integer arithmetic, cstln_receiver.hip: nearest point by the signs, second
+// nearest = flip the coordinate of smaller magnitude: d1 − min(d1 + 4·53·min(|I|,|Q|), 32767)) and the decision `sym`, as the 32 bits of an
+// lsdr_softsymbol {int16 cost; uint8 symbol; uint8 pad = 0}.  |I|, |Q| ≤ 128: every product fits 24 bits.
+__device__ __forceinline__ unsigned rxb_soft_word(int Ii, int Qi, unsigned sym) {
+  const int a = Ii < 0 ? -Ii : Ii, b = Qi < 0 ? -Qi : Qi;
+  const int da = a - 53, db = b - 53;
+  const int d1 = __mul24(da, da) + __mul24(db, db);
+  const int d2 = d1 + __mul24(212, a < b ? a : b);
+  const int cost = d1 - (d2 > 32767 ? 32767 : d2);
+  return ((unsigned)cost & 0xffffu) | (sym << 16);
+}
+
 // LDS staging of the lean tiles: 32 samples per stage + 16 of look-ahead (the next symbol's pair is read up to 3 samples ahead, a timing
 // excursion walks up to omega + 2 ≤ 10): 112-byte rows, 7 KiB per wavefront — 22 wavefronts per CU where the 64-sample stages of
 // rx_tile_tol (11 KiB) allow 14; this kernel lives on wavefronts per SIMD (VALU issue, a dependent chain per symbol).
@@ -231,7 +251,7 @@ struct rxb_stage {
 };
 static_assert(rxb_stage::kRowBytes % 16 == 0 && kChunk % rxb_stage::kStage == 0, "stage geometry");
 
-template <bool NOTCH>
+template <bool NOTCH, bool SOFT>
 __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, unsigned j0, int lane, char *lds) {
   typedef rxb_stage ST;
   constexpr int kStage = ST::kStage, kRowBytes = ST::kRowBytes, kStageLoads = ST::kRowBytes / 16;
@@ -289,6 +309,28 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
 
   unsigned hacc = 0, hcnt = 0, hwarm = 0, hnwarm = 0, got = 0;
   unsigned *const hcol = cap.hstage + j;
+  // SOFT: body symbol k goes to byte 4·(k·hpitch + j) of sstage (one row of `hpitch` dwords per symbol step: the 64 lanes of the wavefront
+  // are 64 consecutive tiles and write 64 consecutive dwords; a capture's staging is below 4 GiB, so k and 4·hpitch fit 24 bits:
+  // lsdr_rxb_create_ex)
+  const unsigned srow = 4u * (unsigned)cap.hpitch;
+  // SOFT: the amplitude the COSTS are taken at.  A cost is proportional to the sampled point's amplitude, so the soft records need the
+  // gain the serial receiver has at this tile — its power estimate is an average over the last hundred chunks (kest = 0.01 per chunk,
+  // sdr.h:867-870), which a warm-up of a few chunks cannot reproduce from the constructed state (the tile's own gain stays some per cent
+  // off for its whole length: harmless for signs, a bias on every cost).  The estimator's input, |interpolated sample|², does not depend
+  // on the gain: the tile averages it over the warm-up's symbols (`pavg`, a running mean of weight 1/128 per symbol: ≈ the last 250
+  // symbols, the timing loop has settled by then) and starts, at the body's first sample, a second estimator from the EXPECTED serial
+  // value after cb + Wc chunks, mean + (1 − kest)^(cb+Wc)·(constructed − mean), updated per chunk like the first (`pavg` again).  The
+  // record's coordinates are the sampled point times crat = gain(second) / gain(first), folded and truncated like the table's index.
+  // The LOOPS keep the first gain, so timing, carrier and the seam records are those of the packed tiles (whose sensitivity is measured,
+  // DESIGN §4.5): run at the second gain they slipped a symbol at noise 20 where the reference does not.
+  float pavg = est_insp, crat = 1.0f;
+  auto soft_gain = [&](float est2) { crat = (est2 > 0.f) ? __builtin_sqrtf(est_insp * __builtin_amdgcn_rcpf(est2)) : 1.0f; };
+  auto soft_record = [&](float svr, float svi) {
+    float Is = svr * crat, Qs = svi * crat;
+    if (__builtin_fmaxf(__builtin_fabsf(Is), __builtin_fabsf(Qs)) > 127.0f) lut_halve(Is, Qs);
+    const int Ic = (int)Is, Qc = (int)Qs;
+    return rxb_soft_word(Ic, Qc, (((unsigned)Ic >> 31) << 1) | ((unsigned)Qc >> 31));
+  };
   float mu_begin = 0.f, phase_begin = 0.f;
   int n = 0;                                     // sample of the next symbol (tile-relative)
   unsigned x0w = 0, x1w = 0;                     // the cu8 items of samples n and n + 1
@@ -303,6 +345,10 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
       const float over = (float)(n - ci * kChunk);
       mu_begin = mu + over; phase_begin = phase - over * freqw;
       got = hcnt; hwarm = hacc; hnwarm = hcnt < 16u ? hcnt : 16u; hcnt = 0;
+      if (SOFT && got) {
+        pavg = __builtin_fmaf(__builtin_exp2f((float)(cb + Wc) * __builtin_log2f(k1)), S0->est_insp - pavg, pavg);
+        soft_gain(pavg);
+      }
     }
     // sampler->update_freq(freqw), sdr.h:790: the partner sample's extra rotation e^{−j·freqw}, constant over the chunk
     const float frev = freqw * (-1.0f / 65536.0f);
@@ -316,6 +362,8 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
       }
     }
     const unsigned cnt0 = hcnt;
+    const bool wlast = ci + 1 == nwarm;           // (SOFT: the last warm-up chunk; its symbols at the gain estimated so far)
+    if (SOFT && active && wlast) soft_gain(__builtin_fmaf(__builtin_exp2f((float)(cb + Wc) * __builtin_log2f(k1)), S0->est_insp - pavg, pavg));
     float g0r = 0.f, g0i = 0.f;                  // last interpolated sample of the chunk, before derotation (|.|² feeds the AGC)
 #pragma unroll 1
     for (int sb = 0; sb < kChunk / kStage; ++sb) {
@@ -349,6 +397,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
         // linear_sampler::interp (sdr.h:614-623), one derotation
         const float q1r = __builtin_fmaf(o1r, cf, -(o1i * sf)), q1i = __builtin_fmaf(o1r, sf, o1i * cf);
         g0r = __builtin_fmaf(mu, q1r - o0r, o0r); g0i = __builtin_fmaf(mu, q1i - o0i, o0i);
+        if (SOFT && !BODY) pavg = __builtin_fmaf(__builtin_fmaf(g0r, g0r, __builtin_fmaf(g0i, g0i, -pavg)), 1.0f / 128.0f, pavg);
         const float prev = phase * (-1.0f / 65536.0f);
         const float ear = __builtin_amdgcn_cosf(prev) * agc, eai = __builtin_amdgcn_sinf(prev) * agc;
         const float svr = __builtin_fmaf(g0r, ear, -(g0i * eai)), svi = __builtin_fmaf(g0r, eai, g0i * ear);
@@ -380,7 +429,10 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
         mu = mu2 - kf;
         phase = __builtin_fmaf(kf, freqw, phase);
         ++hcnt;
-        if (BODY) { if ((hcnt & 15u) == 0) hcol[(unsigned long long)((hcnt >> 4) - 1) * cap.hpitch] = hacc; }
+        if (SOFT) {
+          if (BODY) *reinterpret_cast<unsigned *>(reinterpret_cast<char *>(cap.sstage) + (__umul24(hcnt - 1u, srow) + 4u * j)) = soft_record(svr, svi);
+          else if (wlast) cap.spre[j] = soft_record(svr, svi);                 // (the last one written is the warm-up's last symbol)
+        } else if (BODY) { if ((hcnt & 15u) == 0) hcol[(unsigned long long)((hcnt >> 4) - 1) * cap.hpitch] = hacc; }
         const bool one = ki == 1;
         x0w = one ? x1w : r2; x1w = one ? r2 : r3;
         if (NOTCH) { sr = one ? t0r : t1r; si = one ? t0i : t1i; }
@@ -407,6 +459,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
         const float insp = g0r * g0r + g0i * g0i;
         est_insp = __builtin_fmaf(insp, kk, est_insp * k1);
         if (est_insp) agc = kCstlnAmp / __builtin_sqrtf(est_insp);
+        if (SOFT && body) { pavg = __builtin_fmaf(insp, kk, pavg * k1); soft_gain(pavg); }
       }
       if (!C.allow_drift) {                                                  // sdr.h:895-898
         if (freqw < min_f || freqw > max_f) freqw = (max_f + min_f) / 2;
@@ -417,7 +470,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
     if (nchunks <= nwarm) { mu_begin = mu; phase_begin = phase; got = hcnt; hwarm = hacc; hnwarm = hcnt < 16u ? hcnt : 16u; hcnt = 0; }   // (never: a tile has a body)
     const float over_end = (float)(n - nchunks * kChunk);     // … and AT the sample behind the tile's last one
     mu += over_end; phase -= over_end * freqw;
-    if (hcnt & 15u) hcol[(unsigned long long)(hcnt >> 4) * cap.hpitch] = hacc << (2 * (16 - (hcnt & 15u)));
+    if (!SOFT && (hcnt & 15u)) hcol[(unsigned long long)(hcnt >> 4) * cap.hpitch] = hacc << (2 * (16 - (hcnt & 15u)));
     rx_tile_info_h th;
     th.mu_begin = mu_begin; th.phase_begin = phase_begin; th.mu_end = mu; th.phase_end = phase;
     th.count = hcnt; th.has_pre = got ? 1u : 0u; th.n_warm = hnwarm; th.warm_tail = hwarm; th.body_tail = hacc;
@@ -426,8 +479,8 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
   }
 }
 
-template <bool NOTCH>
-__global__ __launch_bounds__(64) void k_rxb_tiles(rxb_args A) {
+template <bool NOTCH, bool SOFT>
+__device__ __forceinline__ void rxb_tiles_body(const rxb_args &A) {
   __shared__ __attribute__((aligned(16))) char lds[64 * rxb_stage::kRowBytes];
   const rxb_cap &cap = A.caps[blockIdx.y];
   if (blockIdx.x == 0) {
@@ -438,15 +491,21 @@ __global__ __launch_bounds__(64) void k_rxb_tiles(rxb_args A) {
       a.in = cap.in; a.total_chunks = cap.total_chunks; a.first_chunks = A.warm_chunks; a.tile_chunks = A.tile_chunks; a.warm_chunks = A.warm_chunks;
       a.n_tiles = cap.n_tiles; a.lanes_per_wave = 64; a.dbg = 0; a.stage_stride = 0; a.stage = nullptr; a.wstage = nullptr; a.wstride = 0;
       a.info = nullptr; a.hstage = cap.hstage; a.hpitch = cap.hpitch; a.hinfo = cap.hinfo; a.ema = cap.ema_scratch; a.ema_wave = cap.ema_scratch + 1;
+      if (SOFT) a.stage = reinterpret_cast<lsdr_softsymbol *>(cap.sstage);
       a.state = A.state0; a.state_next = cap.state_end; a.meas = nullptr; a.meas_base = 0; a.cstln = nullptr; a.C = A.C; a.T = A.T;
-      rx_tile_exact<1, LSDR_IN_CU8, true>(a);
+      rx_tile_exact<1, LSDR_IN_CU8, true, SOFT>(a);
     }
     return;
   }
   const unsigned j0 = 1u + (blockIdx.x - 1u) * 64u;
   if (j0 >= cap.n_tiles) return;
-  rxb_tile<NOTCH>(A, cap, j0, (int)threadIdx.x, lds);
+  rxb_tile<NOTCH, SOFT>(A, cap, j0, (int)threadIdx.x, lds);
 }
+template <bool NOTCH>
+__global__ __launch_bounds__(64) void k_rxb_tiles(rxb_args A) { rxb_tiles_body<NOTCH, false>(A); }
+// the soft tiles: held to the packed tiles' five waves per SIMD (the notch variant's live values come to one register more)
+template <bool NOTCH>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_rxb_tiles_soft(rxb_args A) { rxb_tiles_body<NOTCH, true>(A); }
 
 __global__ __launch_bounds__(kSeamBlock) void k_rxb_seam(rxb_args A, float omega, int R, float quad, const uint8_t *relabel) {
   const rxb_cap &cap = A.caps[blockIdx.y];
@@ -459,6 +518,78 @@ __global__ __launch_bounds__(64) void k_rxb_compact(rxb_args A, int R, float qua
   if (blockIdx.x * (64u / kRxbCompactLanes) >= cap.n_tiles) return;
   rx_compact_h_body<rx_state_dev, (int)kRxbCompactLanes>(cap.hstage, cap.hpitch, cap.hinfo, cap.fix, cap.part, relabel, cap.n_tiles, R, quad, cap.out_words, 0ull,
                                   cap.state_end, cap.res);
+}
+
+// Compaction of the soft tile columns.  One workgroup of 256 per (64 consecutive tiles × 64 symbol steps): the 64 × 64 dwords come out of
+// the transposed staging row by row (64 consecutive dwords per row), turn in LDS, and leave tile by tile — each tile's 64 symbols are 256
+// consecutive bytes of the output, relabelled by the tile's accumulated quadrant step (the symbol byte only: the cost does not depend on
+// the quadrant).  blockIdx.x = tile group · row_blocks + row block; the row blocks behind a group's longest tile leave at once.  The 64
+// tiles of a group lie in one seam block (kSeamBlock is a multiple of 64), so `base` is the total of the seam blocks in front of it.
+// Tile group 0's first thread also leaves the capture's totals (rx_compact_h_body's duties) and the contiguous count viterbi_sync reads.
+constexpr unsigned kRxbSoftTile = 64;
+static_assert(kSeamBlock % kRxbSoftTile == 0, "the tiles of a soft compaction workgroup share their seam block");
+__global__ __launch_bounds__(256) void k_rxb_compact_soft(rxb_args A, unsigned row_blocks, int R, float quad, const uint8_t *relabel) {
+  const rxb_cap &cap = A.caps[blockIdx.y];
+  const unsigned n_tiles = cap.n_tiles;
+  const unsigned grp = blockIdx.x / row_blocks, rb = blockIdx.x - grp * row_blocks;
+  const unsigned j0 = grp * kRxbSoftTile, k0 = rb * kRxbSoftTile;
+  if (j0 >= n_tiles) return;
+  const unsigned rmask = (unsigned)R - 1;
+  const unsigned nparts = (n_tiles + kSeamBlock - 1) / kSeamBlock, mypart = j0 / kSeamBlock;
+  const unsigned tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  if (blockIdx.x == 0 && tid == 0) {
+    rx_seam_result sr; sr.total = 0; sr.rot_final = 0; sr.ndup = 0; sr.nmiss = 0; sr.nbad = 0; sr.freq_tap = rx_freq_tap(cap.state_end);
+    for (unsigned i = 0; i < nparts; ++i) {
+      sr.total += cap.part[i].cnt; sr.rot_final = (sr.rot_final + cap.part[i].rot) & rmask;
+      sr.ndup += cap.part[i].ndup; sr.nmiss += cap.part[i].nmiss; sr.nbad += cap.part[i].nbad;
+    }
+    *cap.res = sr;
+    *cap.count_out = sr.total;
+    if (sr.rot_final) rx_rotate_back(cap.state_end, sr.rot_final, quad);
+  }
+  __shared__ unsigned s_cnt[kRxbSoftTile], s_skip[kRxbSoftTile], s_map[kRxbSoftTile], s_max;
+  __shared__ long long s_Q[kRxbSoftTile];
+  __shared__ unsigned s_t[kRxbSoftTile][kRxbSoftTile + 1];
+  unsigned long long base = 0;
+  unsigned brot = 0;
+  for (unsigned i = 0; i < mypart; ++i) { base += cap.part[i].cnt; brot += cap.part[i].rot; }      // (uniform; a handful of records)
+  if (tid == 0) s_max = 0;
+  __syncthreads();
+  if (tid < kRxbSoftTile) {
+    unsigned cnt = 0, skip = 0, map4 = 0;
+    long long Q = 0;
+    if (j0 + tid < n_tiles) {
+      const rx_tile_fix f = cap.fix[j0 + tid];
+      cnt = cap.hinfo[j0 + tid].count;
+      skip = f.drop_first ? 1u : 0u;
+      const unsigned ins = f.insert_pre ? 1u : 0u;
+      const long long D = (long long)(base + f.out_offset);
+      Q = D + (long long)ins - (long long)skip;                         // body symbol k goes to out[Q + k]
+      map4 = hs2_map4(relabel + ((f.rot + brot) & rmask) * 256);
+      if (ins && rb == 0) {                                             // the warm-up's last symbol belongs to this tile
+        const unsigned v = cap.spre[j0 + tid];
+        cap.out_soft[D] = (v & 0xff00ffffu) | (((map4 >> (2 * ((v >> 16) & 3u))) & 3u) << 16);
+      }
+      atomicMax(&s_max, cnt);
+    }
+    s_cnt[tid] = cnt; s_skip[tid] = skip; s_map[tid] = map4; s_Q[tid] = Q;
+  }
+  __syncthreads();
+  if (k0 >= s_max) return;                                              // (uniform)
+  const unsigned cnt_l = s_cnt[lane];
+#pragma unroll 4
+  for (unsigned r = wv; r < kRxbSoftTile; r += 4) {                     // row k0 + r: 64 consecutive dwords
+    const unsigned k = k0 + r;
+    if (k < cnt_l) s_t[lane][r] = cap.sstage[(unsigned long long)k * cap.hpitch + j0 + lane];
+  }
+  __syncthreads();
+  for (unsigned t = wv; t < kRxbSoftTile; t += 4) {                     // tile j0 + t: 64 consecutive symbols
+    const unsigned k = k0 + lane;
+    if (k < s_cnt[t] && k >= s_skip[t]) {
+      const unsigned v = s_t[t][lane];
+      cap.out_soft[s_Q[t] + (long long)k] = (v & 0xff00ffffu) | (((s_map[t] >> (2 * ((v >> 16) & 3u))) & 3u) << 16);
+    }
+  }
 }
 
 #endif  // LSDR_RXB_DEVICE_H

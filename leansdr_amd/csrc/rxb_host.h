@@ -24,6 +24,10 @@ struct lsdr_rxb {
   size_t geom_samples;             // n_samples the detect-point tables on the device were built for
   unsigned n_det, n_pre, n_tiles; unsigned long long total_chunks;
   hipEvent_t tev0, tev1; bool timing; double time_ms; unsigned time_n; bool tev_pending;
+  bool soft;                       // soft symbols out (the Viterbi engine): sstage / spre / out_soft instead of hstage / out_words
+  unsigned srows;                  // rows (symbol steps) of a capture's transposed soft staging
+  size_t soft_cap;                 // soft symbols per capture in out_soft
+  unsigned long long *d_counts;    // [n] contiguous: soft symbols of every capture after the launch
   hipEvent_t ev_pre, ev_tiles;      // hand-overs between the tile stream and the auxiliary stream (lsdr_rxb_launch with aux)
 };
 
@@ -51,13 +55,17 @@ static rxb_geom rxb_geometry(const lsdr_rxb *b, size_t n_samples) {
   return g;
 }
 
-int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **out) {
+int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **out) { return lsdr_rxb_create_ex(c, cfg, 0, 1.0f, out); }
+
+// soft != 0: lsdr_softsymbol records out (rxb_device.h's soft tiles); pll_adjustment: cstln_receiver::pll_adjustment (sdr.h:777: divides
+// freq_beta only), 1 in leandvb's default graph, 6 behind viterbi_sync (leandvb.cc:498-501) — given here as the factor 1/6
+int lsdr_rxb_create_ex(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, lsdr_rxb **out) {
   LSDR_ARG(c && cfg && out && cfg->n_captures >= 1 && cfg->n_captures <= 4096 && cfg->max_samples >= 4096);
   LSDR_ARG(cfg->anf == 0 || cfg->anf == 1);
   lsdr_rx_cfg rc;
   memset(&rc, 0, sizeof(rc));
   rc.sampler = LSDR_SAMP_LINEAR; rc.cstln = LSDR_QPSK; rc.fec = cfg->fec; rc.omega = cfg->omega; rc.freq = 0.f;
-  rc.meas_decimation = 1048576; rc.pll_adjustment = 1.0f; rc.allow_drift = 0; rc.kest = 0.01f; rc.mode = LSDR_RX_TILED;
+  rc.meas_decimation = 1048576; rc.pll_adjustment = pll_adjustment; rc.allow_drift = 0; rc.kest = 0.01f; rc.mode = LSDR_RX_TILED;
   rc.in_format = LSDR_IN_CU8; rc.out_format = LSDR_SYM_HARD2;
   if (!(cfg->omega >= 1.0f && cfg->omega <= 8.0f)) { lsdr_set_error("capture_batch: omega (samples per symbol) must be in [1, 8], got %g", (double)cfg->omega); return LSDR_E_UNSUPPORTED; }
   const unsigned L = cfg->tile_len ? cfg->tile_len : 4096u, W = cfg->tile_warmup ? cfg->tile_warmup : 512u;
@@ -71,6 +79,7 @@ int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **o
   lsdr_rxb *b = new lsdr_rxb();
   b->ctx = c; b->proto = proto; b->n = (unsigned)cfg->n_captures; b->max_samples = cfg->max_samples; b->anf = cfg->anf;
   b->Lc = L / kChunk; b->Wc = W / kChunk;
+  b->soft = soft != 0;
   b->pre_block = (L % 4096u) ? 2048u : 4096u;
   b->nk = cfg->notch_k > 0.f ? cfg->notch_k : 0.002f;                          // sdr.h:56
   b->notch_decimation = cfg->notch_decimation > 0 ? cfg->notch_decimation : 1024 * kDetN;
@@ -92,6 +101,12 @@ int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **o
   b->hwords = stage_stride / 16 + 2;
   b->hpitch = ((unsigned long long)b->max_tiles + 63) & ~63ull;
   b->words_cap = (size_t)((unsigned long long)g.chunks * sym_per_chunk / 16 + b->max_tiles + 64);
+  // soft staging: a symbol step moves at least one sample on, so a tile body of Lc (tile 0: Wc) chunks holds at most that many samples' symbols
+  b->srows = (b->Wc > b->Lc ? b->Wc : b->Lc) * (unsigned)kChunk + 1u;
+  b->soft_cap = (size_t)((unsigned long long)g.chunks * sym_per_chunk + b->max_tiles + 64);
+  if (b->soft && b->hpitch * b->srows * sizeof(unsigned) >= (1ull << 32)) {       // (the soft tiles address a capture's staging with 32 bits)
+    lsdr_set_error("capture_batch: %zu samples per capture are too many for the soft staging at tile_len %u", b->max_samples, L); return LSDR_E_UNSUPPORTED;
+  }
   b->caps.assign(b->n, rxb_cap());
   LSDR_HIP(hipMalloc((void **)&b->d_caps, b->n * sizeof(rxb_cap)));
   LSDR_HIP(hipHostMalloc((void **)&b->h_caps, b->n * sizeof(rxb_cap), hipHostMallocDefault));
@@ -103,6 +118,8 @@ int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **o
   LSDR_HIP(hipMalloc((void **)&b->d_state0, sizeof(rx_state_dev)));
   LSDR_HIP(hipMemcpy(b->d_state0, &proto->st_initial, sizeof(rx_state_dev), hipMemcpyHostToDevice));
   LSDR_HIP(hipMalloc((void **)&b->d_ema, 2 * b->n * sizeof(rx_ema_map)));
+  LSDR_HIP(hipMalloc((void **)&b->d_counts, b->n * sizeof(unsigned long long)));
+  LSDR_HIP(hipMemset(b->d_counts, 0, b->n * sizeof(unsigned long long)));
   LSDR_HIP(hipMalloc((void **)&b->d_iv_of_block, (size_t)b->max_blocks * sizeof(unsigned)));
   LSDR_HIP(hipMalloc((void **)&b->d_det_block, (size_t)(b->max_det + 1) * sizeof(unsigned)));
   {
@@ -114,11 +131,17 @@ int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **o
   for (unsigned i = 0; i < b->n; ++i) {
     rxb_cap &cp = b->caps[i];
     memset(&cp, 0, sizeof(cp));
-    LSDR_TRY(rxb_alloc(b, (void **)&cp.hstage, (size_t)b->hpitch * b->hwords * sizeof(unsigned)));
+    LSDR_TRY(rxb_alloc(b, (void **)&cp.hstage, b->soft ? 0 : (size_t)b->hpitch * b->hwords * sizeof(unsigned)));
     LSDR_TRY(rxb_alloc(b, (void **)&cp.hinfo, (size_t)b->max_tiles * sizeof(rx_tile_info_h)));
     LSDR_TRY(rxb_alloc(b, (void **)&cp.fix, (size_t)b->max_tiles * sizeof(rx_tile_fix)));
     LSDR_TRY(rxb_alloc(b, (void **)&cp.part, (size_t)((b->max_tiles + kSeamBlock - 1) / kSeamBlock) * sizeof(rx_seam_part)));
-    LSDR_TRY(rxb_alloc(b, (void **)&cp.out_words, b->words_cap * sizeof(unsigned)));
+    LSDR_TRY(rxb_alloc(b, (void **)&cp.out_words, b->soft ? 0 : b->words_cap * sizeof(unsigned)));
+    if (b->soft) {
+      LSDR_TRY(rxb_alloc(b, (void **)&cp.sstage, (size_t)b->hpitch * b->srows * sizeof(unsigned)));
+      LSDR_TRY(rxb_alloc(b, (void **)&cp.spre, (size_t)b->max_tiles * sizeof(unsigned)));
+      LSDR_TRY(rxb_alloc(b, (void **)&cp.out_soft, b->soft_cap * sizeof(unsigned)));
+    }
+    cp.count_out = b->d_counts + i;
     cp.res = b->d_res + i; cp.state_end = b->d_state_end + i; cp.ema_scratch = b->d_ema + 2 * i;
     cp.hpitch = b->hpitch;
     if (b->anf) {
@@ -140,7 +163,7 @@ void lsdr_rxb_destroy(lsdr_rxb *b) {
   (void)hipStreamSynchronize(b->ctx->stream);
   for (void *p : b->owned) (void)hipFree(p);
   (void)hipFree(b->d_caps); if (b->h_caps) (void)hipHostFree(b->h_caps);
-  (void)hipFree(b->d_res); if (b->h_res) (void)hipHostFree(b->h_res); (void)hipFree(b->d_state_end); (void)hipFree(b->d_state0); (void)hipFree(b->d_ema);
+  (void)hipFree(b->d_res); if (b->h_res) (void)hipHostFree(b->h_res); (void)hipFree(b->d_state_end); (void)hipFree(b->d_state0); (void)hipFree(b->d_ema); (void)hipFree(b->d_counts);
   (void)hipFree(b->d_iv_of_block); (void)hipFree(b->d_det_block); (void)hipFree(b->d_om);
   if (b->tev0) (void)hipEventDestroy(b->tev0);
   if (b->tev1) (void)hipEventDestroy(b->tev1);
@@ -197,6 +220,7 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
   LSDR_HIP(hipMemcpyAsync(b->d_caps, b->h_caps, b->n * sizeof(rxb_cap), hipMemcpyHostToDevice, sa));
   if (!g.chunks) {
     LSDR_HIP(hipMemsetAsync(b->d_res, 0, b->n * sizeof(rx_seam_result), sa));
+    LSDR_HIP(hipMemsetAsync(b->d_counts, 0, b->n * sizeof(unsigned long long), sa));
     LSDR_HIP(hipMemcpyAsync(b->h_res, b->d_res, b->n * sizeof(rx_seam_result), hipMemcpyDeviceToHost, sa));
     return LSDR_OK;
   }
@@ -215,7 +239,10 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
   const unsigned blocks = 1 + (g.n_tiles - 1 + 63) / 64;
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_pre, sa)); LSDR_HIP(hipStreamWaitEvent(st, b->ev_pre, 0)); }
   if (b->timing) { LSDR_HIP(hipEventRecord(b->tev0, st)); }
-  if (notch) hipLaunchKernelGGL(k_rxb_tiles<true>, dim3(blocks, b->n), dim3(64), 0, st, A);
+  if (b->soft) {
+    if (notch) hipLaunchKernelGGL(k_rxb_tiles_soft<true>, dim3(blocks, b->n), dim3(64), 0, st, A);
+    else hipLaunchKernelGGL(k_rxb_tiles_soft<false>, dim3(blocks, b->n), dim3(64), 0, st, A);
+  } else if (notch) hipLaunchKernelGGL(k_rxb_tiles<true>, dim3(blocks, b->n), dim3(64), 0, st, A);
   else hipLaunchKernelGGL(k_rxb_tiles<false>, dim3(blocks, b->n), dim3(64), 0, st, A);
   if (b->timing) { LSDR_HIP(hipEventRecord(b->tev1, st)); b->tev_pending = true; }
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_tiles, st)); LSDR_HIP(hipStreamWaitEvent(sa, b->ev_tiles, 0)); }
@@ -223,14 +250,23 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
   const float quad = 65536.0f / R;
   hipLaunchKernelGGL(k_rxb_seam, dim3((g.n_tiles + kSeamBlock - 1) / kSeamBlock, b->n), dim3(kSeamBlock), 0, sa, A, r->omega, R, quad,
                      (const uint8_t *)r->d_relabel);
-  hipLaunchKernelGGL(k_rxb_compact, dim3((g.n_tiles * kRxbCompactLanes + 63) / 64, b->n), dim3(64), 0, sa, A, R, quad, (const uint8_t *)r->d_relabel);
+  if (b->soft) {
+    const unsigned row_blocks = (b->srows + kRxbSoftTile - 1) / kRxbSoftTile;
+    hipLaunchKernelGGL(k_rxb_compact_soft, dim3(((g.n_tiles + kRxbSoftTile - 1) / kRxbSoftTile) * row_blocks, b->n), dim3(256), 0, sa, A, row_blocks, R, quad,
+                       (const uint8_t *)r->d_relabel);
+  } else
+    hipLaunchKernelGGL(k_rxb_compact, dim3((g.n_tiles * kRxbCompactLanes + 63) / 64, b->n), dim3(64), 0, sa, A, R, quad, (const uint8_t *)r->d_relabel);
   LSDR_HIP(hipGetLastError());
   LSDR_HIP(hipMemcpyAsync(b->h_res, b->d_res, b->n * sizeof(rx_seam_result), hipMemcpyDeviceToHost, sa));
   return LSDR_OK;
 }
 
-const uint32_t *lsdr_rxb_words(const lsdr_rxb *b, unsigned i) { return b && i < b->n ? b->caps[i].out_words : nullptr; }
+const uint32_t *lsdr_rxb_words(const lsdr_rxb *b, unsigned i) { return b && !b->soft && i < b->n ? b->caps[i].out_words : nullptr; }
 size_t lsdr_rxb_words_cap(const lsdr_rxb *b) { return b ? b->words_cap : 0; }
+// the soft engine: capture i's compacted soft symbols, their capacity, and the contiguous device array [n] of their counts
+const lsdr_softsymbol *lsdr_rxb_soft(const lsdr_rxb *b, unsigned i) { return b && b->soft && i < b->n ? reinterpret_cast<const lsdr_softsymbol *>(b->caps[i].out_soft) : nullptr; }
+size_t lsdr_rxb_soft_cap(const lsdr_rxb *b) { return b && b->soft ? b->soft_cap : 0; }
+const unsigned long long *lsdr_rxb_counts_dev(const lsdr_rxb *b) { return b ? b->d_counts : nullptr; }
 // device array [n]: .total = packed decisions of capture i after the launch (struct rx_seam_result: 8-byte total first)
 const void *lsdr_rxb_results_dev(const lsdr_rxb *b, size_t *stride) { if (stride) *stride = sizeof(rx_seam_result); return b ? b->d_res : nullptr; }
 unsigned lsdr_rxb_tiles(const lsdr_rxb *b) { return b ? b->n_tiles : 0; }

@@ -14,6 +14,10 @@
 //                     per-packet countdown drops at the third consecutive sync byte that is not the predicted one after a good one
 //   k_tail_book       finishes that call's bookkeeping (one thread), then runs mpeg_sync::run() on what is left until nothing moves
 //                     (a dropped lock: search, relock, decode — rare, one workgroup), and fixes the deinterleaver's packet count
+//   k_tail_acquire_bytes   the Viterbi engine's chain has no deconvol_sync: viterbi_sync's bytes are already in `bytes`, mpeg_sync was built
+//                     with deconv = NULL (leandvb.cc:530, 563) and its search is a function of the byte stream alone (dvb.h:755-769,
+//                     798-840).  Searches until the lock (or the end), then plans mpeg_sync's locked bulk call like k_tail_acquire;
+//                     k_tail_deconv is not launched, the rest of the tail is the same
 //   k_tail_deint / k_tail_rs / k_tail_derand_scan / k_tail_derand_apply   the packet kernels, counts read from the record
 #ifndef LSDR_TAIL_DEVICE_H
 #define LSDR_TAIL_DEVICE_H
@@ -29,7 +33,10 @@ struct tail_result {             // per capture, host-visible when the batch has
   unsigned long long first_lock_byte;   // deconvolved-stream offset of the first lock (~0: never locked)
 };
 
+struct tail_vit { unsigned long long bytes; unsigned alignment, pad; };   // per capture: what viterbi_sync committed, its current_sync
+
 struct tail_cap {
+  const tail_vit *vit;                   // the Viterbi engine (k_tail_acquire_bytes): `bytes` is filled already; null: deconvol_sync's chain
   const unsigned *words;                 // packed decisions
   const unsigned long long *nsym;        // → how many (device)
   unsigned char *bytes, *mpeg, *rs, *rts, *ts;
@@ -191,6 +198,45 @@ __global__ __launch_bounds__(256) void k_tail_acquire(tail_args A) {
   }
 }
 
+__global__ __launch_bounds__(256) void k_tail_acquire_bytes(tail_args A) {
+  tail_cap &tc = A.caps[blockIdx.y];
+  __shared__ msync_sh M;
+  __shared__ int s_again;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    tc.locked = (int)tc.vit->alignment; tc.skip = 0;
+    for (int i = 0; i < 4; ++i) { tc.n_in[i] = 0; tc.n_out[i] = 0; tc.carry[i].in = 0; tc.carry[i].out = 0; }
+    tc.pos = *tc.nsym; tc.br = tc.mw = 0;
+    tc.bw = tc.vit->bytes < tc.byte_cap ? tc.vit->bytes : tc.byte_cap;
+    tc.n_pk = tc.n_ts = tc.rs_errs = 0; tc.next_sync_calls = 0; tc.first_lock = ~0ull;
+    tc.bulk_P = 0; tc.drop_at = ~0ull; tc.last_ok = -1;
+    tc.plan.n_bytes = 0;
+    M.S = A.ms0;
+  }
+  __syncthreads();
+  // mpeg_sync::run() until it locks or nothing moves (what it asks of a deconvolver — call_next_sync — has nobody to go to: dvb.h:777)
+  do {
+    __syncthreads();
+    msync_run_body(M, tc.bytes + tc.br, tc.bw - tc.br, tc.mpeg + tc.mw, tc.byte_cap - tc.mw, tid);
+    if (tid == 0) {
+      if (M.S.synchronized && tc.first_lock == ~0ull) tc.first_lock = tc.br + M.R.consumed;
+      tc.br += M.R.consumed; tc.mw += M.R.produced;
+      s_again = (!M.S.synchronized && (M.R.consumed || M.R.produced)) ? 1 : 0;
+    }
+    __syncthreads();
+  } while (s_again);
+  if (tid == 0) {
+    unsigned long long Pk = 0;
+    if (M.S.synchronized && tc.bw - tc.br >= (unsigned long long)kRS + 1) {
+      Pk = (tc.bw - tc.br - 1) / kRS;
+      const unsigned long long room = (tc.byte_cap - tc.mw) / kRS;
+      if (Pk > room) Pk = room;
+    }
+    tc.bulk_P = Pk;
+    tc.ms = M.S;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_tail_deconv(tail_args A) {
   const tail_cap &tc = A.caps[blockIdx.y];
   const deconv_plan P = tc.plan;
@@ -328,7 +374,7 @@ __global__ __launch_bounds__(256) void k_tail_book(tail_args A) {
     __syncthreads();
     msync_run_body(M, tc.bytes + tc.br, tc.bw - tc.br, tc.mpeg + tc.mw, tc.byte_cap - tc.mw, tid);
     if (tid == 0) {
-      if (M.R.call_next_sync) { ++tc.next_sync_calls; ++tc.locked; if (tc.locked == 4) { tc.locked = 0; tc.skip = 1; } }
+      if (M.R.call_next_sync && !tc.vit) { ++tc.next_sync_calls; ++tc.locked; if (tc.locked == 4) { tc.locked = 0; tc.skip = 1; } }
       tc.br += M.R.consumed; tc.mw += M.R.produced;
       s_again = (M.R.consumed || M.R.produced) ? 1 : 0;
     }

@@ -14,6 +14,8 @@ struct lsdr_tail {
   tail_cap *d_caps;
   tail_result *h_res, *h_res_dev;   // pinned, [n]
   std::vector<void *> owned;
+  bool nodeconv;                    // the Viterbi engine's tail: `bytes` is filled by viterbi_sync (k_tail_acquire_bytes)
+  tail_vit *h_vit, *d_vit;          // nodeconv: [n] pinned staging and device records
 };
 
 static int tail_alloc(lsdr_tail *t, void **p, size_t bytes) {
@@ -23,23 +25,36 @@ static int tail_alloc(lsdr_tail *t, void **p, size_t bytes) {
 }
 
 int lsdr_tail_create(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, lsdr_tail **out) {
+  return lsdr_tail_create_ex(c, n, sym_cap, rate, window, 0, 0, out);
+}
+
+// bytes_per_capture != 0: the tail behind viterbi_sync — no deconvol_sync; every capture's `bytes` buffer takes that many bytes
+int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, int nodeconv, size_t bytes_per_capture, lsdr_tail **out) {
   LSDR_ARG(c && out && n >= 1 && sym_cap >= 1 && window >= 2048);      // (mpeg_sync's search needs 204·8 + 1 bytes in one call)
+  LSDR_ARG(!nodeconv || bytes_per_capture >= 1);
   LSDR_HIP(hipSetDevice(c->device));
   lsdr_tail *t = new lsdr_tail();
-  t->ctx = c; t->n = n; t->sym_cap = sym_cap;
+  t->ctx = c; t->n = n; t->sym_cap = sym_cap; t->nodeconv = nodeconv != 0; t->h_vit = nullptr; t->d_vit = nullptr;
   *out = t;                                                             // (from here on the caller destroys on error)
-  LSDR_TRY(lsdr_deconv_create(c, rate, 0, &t->dec));
+  if (!t->nodeconv) LSDR_TRY(lsdr_deconv_create(c, rate, 0, &t->dec));
   LSDR_TRY(lsdr_derandomizer_create(c, &t->der));
   gf_tables *tab = rs_device_tables(c);
   if (!tab) { lsdr_set_error("capture_batch: cannot allocate GF tables"); return LSDR_E_NOMEM; }
-  const deconv_host &H = t->dec->H;
-  // bytes out of sym_cap symbols (rate pp/(pw/2) bits per symbol) with slack; packets of 204 bytes
-  t->byte_cap = (size_t)((unsigned long long)sym_cap * (unsigned)H.pp / (unsigned)(H.pw / 2) / 8) + 65536;
-  t->pk_cap = t->byte_cap / kRS + 64;
   memset(&t->A, 0, sizeof(t->A));
-  for (int b = 0; b < 8; ++b) t->A.D.deconv[b] = b < H.pp ? H.deconv[b] : 0;
-  t->A.D.pp = H.pp; t->A.D.pw = H.pw;
-  for (int a = 0; a < 4; ++a) for (int s = 0; s < 4; ++s) t->A.luts[a][s] = t->dec->luts[a][s];
+  if (t->nodeconv) {
+    t->byte_cap = (bytes_per_capture + 65536 + 3) & ~(size_t)3;
+    LSDR_HIP(hipMalloc((void **)&t->d_vit, n * sizeof(tail_vit)));
+    LSDR_HIP(hipMemset(t->d_vit, 0, n * sizeof(tail_vit)));
+    LSDR_HIP(hipHostMalloc((void **)&t->h_vit, n * sizeof(tail_vit), hipHostMallocDefault));
+  } else {
+    const deconv_host &H = t->dec->H;
+    // bytes out of sym_cap symbols (rate pp/(pw/2) bits per symbol) with slack; packets of 204 bytes
+    t->byte_cap = (size_t)((unsigned long long)sym_cap * (unsigned)H.pp / (unsigned)(H.pw / 2) / 8) + 65536;
+    for (int b = 0; b < 8; ++b) t->A.D.deconv[b] = b < H.pp ? H.deconv[b] : 0;
+    t->A.D.pp = H.pp; t->A.D.pw = H.pw;
+    for (int a = 0; a < 4; ++a) for (int s = 0; s < 4; ++s) t->A.luts[a][s] = t->dec->luts[a][s];
+  }
+  t->pk_cap = t->byte_cap / kRS + 64;
   memset(&t->A.ms0, 0, sizeof(t->A.ms0));
   t->A.ms0.scan_syncs = 8; t->A.ms0.want_syncs = 4; t->A.ms0.lock_timeout = 4; t->A.ms0.resync_period = 1;      // dvb.h:727-731
   t->A.gtab = tab;
@@ -68,6 +83,7 @@ int lsdr_tail_create(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned
     LSDR_TRY(tail_alloc(t, (void **)&tc.pkt_dst, t->pk_cap * sizeof(long long)));
     tc.byte_cap = t->byte_cap; tc.pk_cap = t->pk_cap;
     tc.res = t->h_res_dev + i;
+    if (t->nodeconv) tc.vit = t->d_vit + i;
   }
   t->A.caps = t->d_caps;
   return LSDR_OK;
@@ -79,16 +95,18 @@ void lsdr_tail_destroy(lsdr_tail *t) {
   for (void *p : t->owned) (void)hipFree(p);
   (void)hipFree(t->d_caps);
   if (t->h_res) (void)hipHostFree(t->h_res);
-  lsdr_deconv_destroy(t->dec);
+  (void)hipFree(t->d_vit);
+  if (t->h_vit) (void)hipHostFree(t->h_vit);
+  if (t->dec) lsdr_deconv_destroy(t->dec);
   lsdr_derandomizer_destroy(t->der);
   delete t;
 }
 
 // Inputs of capture i: its packed decisions and where their count will be (device memory, 8 bytes).  Uploads the records.
 int lsdr_tail_bind(lsdr_tail *t, const uint32_t *const *words, const void *counts_dev, size_t count_stride) {
-  LSDR_ARG(t && words && counts_dev);
+  LSDR_ARG(t && (words || t->nodeconv) && counts_dev);
   for (unsigned i = 0; i < t->n; ++i) {
-    t->caps[i].words = words[i];
+    t->caps[i].words = words ? words[i] : nullptr;
     t->caps[i].nsym = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(counts_dev) + i * count_stride);
   }
   LSDR_HIP(hipMemcpy(t->d_caps, t->caps.data(), t->n * sizeof(tail_cap), hipMemcpyHostToDevice));
@@ -97,6 +115,16 @@ int lsdr_tail_bind(lsdr_tail *t, const uint32_t *const *words, const void *count
 
 // Queues the tail of every capture on the context's stream.  `before_ts`: an event the kernel that WRITES the TS buffers waits for (the
 // download of the previous batch's TS), or null.
+// nodeconv: what viterbi_sync committed for every capture (bytes already in lsdr_tail_bytes_dev(i)) and its alignment; queued on the
+// context's stream in front of the next lsdr_tail_launch.  The previous launch must have completed (single-buffered staging).
+int lsdr_tail_set_bytes(lsdr_tail *t, const unsigned long long *bytes, const unsigned *alignment) {
+  LSDR_ARG(t && t->nodeconv && bytes && alignment);
+  LSDR_HIP(hipSetDevice(t->ctx->device));
+  for (unsigned i = 0; i < t->n; ++i) { t->h_vit[i].bytes = bytes[i]; t->h_vit[i].alignment = alignment[i]; t->h_vit[i].pad = 0; }
+  LSDR_HIP(hipMemcpyAsync(t->d_vit, t->h_vit, t->n * sizeof(tail_vit), hipMemcpyHostToDevice, t->ctx->stream));
+  return LSDR_OK;
+}
+
 int lsdr_tail_launch(lsdr_tail *t, hipEvent_t before_ts) {
   LSDR_ARG(t);
   lsdr_ctx *c = t->ctx;
@@ -107,8 +135,12 @@ int lsdr_tail_launch(lsdr_tail *t, hipEvent_t before_ts) {
   if (wide < 16) wide = 16;
   wide = (wide + 7) / 8 * 8;
   const dim3 grid(wide, t->n);
-  hipLaunchKernelGGL(k_tail_acquire, one, dim3(256), 0, c->stream, t->A);
-  hipLaunchKernelGGL(k_tail_deconv, grid, dim3(256), 0, c->stream, t->A);
+  if (t->nodeconv) {
+    hipLaunchKernelGGL(k_tail_acquire_bytes, one, dim3(256), 0, c->stream, t->A);
+  } else {
+    hipLaunchKernelGGL(k_tail_acquire, one, dim3(256), 0, c->stream, t->A);
+    hipLaunchKernelGGL(k_tail_deconv, grid, dim3(256), 0, c->stream, t->A);
+  }
   hipLaunchKernelGGL(k_tail_realign, grid, dim3(256), 0, c->stream, t->A);
   hipLaunchKernelGGL(k_tail_book, one, dim3(256), 0, c->stream, t->A);
   hipLaunchKernelGGL(k_tail_deint, grid, dim3(256), 0, c->stream, t->A);
@@ -125,6 +157,7 @@ const lsdr_tail_result *lsdr_tail_results(const lsdr_tail *t) { return t ? reint
 const uint8_t *lsdr_tail_ts_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].ts : nullptr; }
 size_t lsdr_tail_ts_cap(const lsdr_tail *t) { return t ? t->pk_cap * kTS : 0; }
 // tests: the deconvolved bytes / the mpeg_sync output of capture i (device pointers; counts in the result record)
+size_t lsdr_tail_byte_cap(const lsdr_tail *t) { return t ? t->byte_cap : 0; }
 const uint8_t *lsdr_tail_bytes_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].bytes : nullptr; }
 const uint8_t *lsdr_tail_mpeg_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].mpeg : nullptr; }
 

@@ -1,0 +1,325 @@
+"""lsdr_capture_batch's Viterbi engine (lsdr_capture_batch_create_viterbi): B independent cu8 captures, each from its first sample to TS by
+leandvb's `--viterbi` graph per capture (auto_notch → cstln_receiver(linear, pll_adjustment / 6) → viterbi_sync → mpeg_sync(deconv = NULL) →
+deinterleaver → rs_decoder → derandomizer), in shared launches.
+
+  * whole job: every capture's TS against the reference BINARY's for the same IQ (`leandvb --u8 -f 2400e3 --sr 2000e3 --cr 1/2 --viterbi`),
+    on captures so noisy that the default graph decodes little or nothing of them, by bench_c1.verify's rule;
+  * front end: the soft symbols — costs included — against the oracle's exact chain under leansdr_amd.tolerance.TOL, tile 0 bit for bit;
+  * Viterbi stage and tail: given the object's own soft symbols, the bytes are a fresh single-stream lsdr_viterbi_run's, and the rest is
+    what the one-block-per-call C ABI produces from those bytes when the host drives it;
+  * a capture's TS and its number of Viterbi rounds do not depend on what else is in the batch.
+
+The reference binary (oracle/_ref/leandvb) is required: where it is missing these tests FAIL.
+"""
+import ctypes as C
+import functools
+import os
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, ROOT)
+
+REFBIN = os.path.join(ROOT, "oracle", "_ref", "leandvb")
+REF_ARGS = ["--u8", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2", "--viterbi"]
+WEAK = [(21, 12), (22, 15), (23, 18), (24, 20)]           # (seed, noise_std): the default graph returns 1446 / 1133 / 4 / 0 packets of 1500
+
+
+@functools.lru_cache(maxsize=None)
+def _capture(n_packets, seed, noise_std):
+    from leansdr_amd import synth_dvbs
+    iq, ts = synth_dvbs.capture_u8(n_packets=n_packets, sps_num=6, sps_den=5, seed=seed, noise_std=noise_std)
+    return np.ascontiguousarray(iq), {bytes(p) for p in np.asarray(ts, np.uint8).reshape(-1, 188)}
+
+
+@functools.lru_cache(maxsize=None)
+def _reference_ts(n_packets, seed, noise_std, n_samples, extra):
+    """The reference binary's TS for the first n_samples (None: all) of a capture; extra: more arguments, e.g. ("--anf", "0")."""
+    assert os.path.exists(REFBIN) and os.access(REFBIN, os.X_OK), "oracle/_ref/leandvb is missing: build() makes it where the reference is present"
+    iq, _ = _capture(n_packets, seed, noise_std)
+    if n_samples is not None:
+        iq = iq[: 2 * n_samples]
+    p = subprocess.run([REFBIN] + REF_ARGS + list(extra), input=iq.tobytes(), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600)
+    return p.stdout
+
+
+def _references(keys):
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        return list(ex.map(lambda k: _reference_ts(*k), keys))
+
+
+def _packets(ts):
+    return [ts[i:i + 188] for i in range(0, len(ts), 188)]
+
+
+def _check_against_reference(got, ref, sent, min_ref_packets, name):
+    """bench_c1.verify's rule with its numbers.  Returns whether the whole TS is identical (recorded, not required)."""
+    import bench_c1
+    rpk, pk = _packets(ref), _packets(got)
+    # condition on the input: the reference decodes this capture
+    assert len(ref) % 188 == 0 and len(rpk) >= min_ref_packets, f"{name}: invalid input, the reference returns {len(rpk)} packets"
+    tail = rpk[bench_c1.SKIP_ACQ:]
+    assert len(tail) > 100 and tail[0] in pk, f"{name}: the reference's packet {bench_c1.SKIP_ACQ} is not in the batch's TS ({len(pk)} packets)"
+    i0 = pk.index(tail[0])
+    m = min(len(tail), len(pk) - i0)
+    assert pk[i0:i0 + m] == tail[:m], f"{name}: differs from the reference behind acquisition"
+    assert len(tail) - m <= 16, f"{name}: {len(tail) - m} of the reference's last packets not reached"
+    assert len(got) % 188 == 0 and all(p in sent for p in pk), f"{name}: a packet that was never transmitted"
+    same = got == ref
+    print(f"{name}: {len(pk)} packets, reference {len(rpk)}, compared {m}, first compared at {i0}, whole TS identical: {same}")
+    return same
+
+
+def _decode(capi, ctx, iqs, n_samples, anf, tile, cb=None):
+    """One batch on a (new, unless given) Viterbi object: (object, results, TS per capture)."""
+    import bench_c1
+    bufs = [ctx.upload(iq[: 2 * n_samples]) for iq in iqs]
+    try:
+        if cb is None:
+            cb = capi.CaptureBatch(ctx, len(iqs), n_samples, bench_c1.OMEGA, anf=anf, tile_len=tile, tile_warmup=512, viterbi=True)
+        res, ts = cb.decode([b.ptr for b in bufs], n_samples)
+    finally:
+        for b in bufs:
+            b.free()
+    return cb, res, ts
+
+
+@pytest.mark.parametrize("tile", [4096, 2048])
+def test_weak_captures_decode_to_the_reference_ts(capi, ctx, tile):
+    """B = 4, anf 0, noise 12 … 20: at 18 and 20 the default engine returns nothing."""
+    caps = [_capture(1500, s, n) for s, n in WEAK]
+    n = len(caps[0][0]) // 2
+    assert n == 2937623 and all(len(c[0]) == 2 * n for c in caps)
+    refs = _references([(1500, s, nz, None, ("--anf", "0")) for s, nz in WEAK])
+    cb, res, ts = _decode(capi, ctx, [c[0] for c in caps], n, 0, tile)
+    try:
+        for i, (s, nz) in enumerate(WEAK):
+            _check_against_reference(ts[i], refs[i], caps[i][1], 1400, f"seed {s} noise {nz} tile {tile}")
+            r = res[i]
+            assert r["locked"] == 1 and r["seam_bad"] == 0 and r["next_sync_calls"] == 0, r
+            st = cb.viterbi_stats(i)
+            assert st["bytes"] == r["bytes_deconv"] and st["current_sync"] == r["alignment"] and st["rounds"] >= 1, (st, r)
+            assert st["batch_rounds"] >= st["rounds"]
+        assert capi.lib.lsdr_capture_batch_words_dev(cb.h, 0) is None
+        assert cb.soft_ptr(4) is None and cb.soft_ptr(-1) is None and capi.lib.lsdr_capture_batch_ts_dev(cb.h, 4) is None
+    finally:
+        cb.close()
+
+
+def test_across_a_detect_point_with_the_notch(capi, ctx):
+    """anf = 1 (leandvb's default), 5.9 M samples: the first detect point is at sample 4 190 208.  Then a short run on the same object."""
+    iq, sent = _capture(3000, 31, 18)
+    n = len(iq) // 2
+    assert n == 5875223
+    iq23, sent23 = _capture(1500, 23, 18)
+    ref, ref_short = _references([(3000, 31, 18, None, ()), (1500, 23, 18, 1000000, ())])
+    cb, res, ts = _decode(capi, ctx, [iq, iq], n, 1, 4096)
+    try:
+        _check_against_reference(ts[0], ref, sent, 2900, "seed 31 noise 18 anf 1")
+        assert ts[0] == ts[1]
+        assert all(r["locked"] == 1 and r["seam_bad"] == 0 and r["next_sync_calls"] == 0 for r in res), res
+        assert len(cb.bins(0)) == 1
+        _, res2, ts2 = _decode(capi, ctx, [iq23, iq23], 1000000, 1, 4096, cb=cb)
+        _check_against_reference(ts2[0], ref_short, sent23, 400, "seed 23 noise 18, 1 000 000 samples, second run")
+        assert ts2[0] == ts2[1]
+        assert all(r["samples"] == (1000000 // 4096 * 4096 - 1) // 128 * 128 for r in res2), res2
+    finally:
+        cb.close()
+
+
+@pytest.mark.parametrize("anf,tile,cw_amp", [(1, 4096, 14.0), (1, 2048, 14.0), (0, 4096, 0.0)])
+def test_soft_symbols_against_the_oracle_chain(capi, ctx, oracle, anf, tile, cw_amp):
+    """cconverter → auto_notch → cstln_receiver(linear, pll_adjustment 1/6): the batch's soft symbols, costs included, against the oracle's
+    sequential exact chain under tolerance.TOL; the symbols of tile 0 bit for bit."""
+    import bench_c1
+    import pyoracle as po
+    from leansdr_amd import tolerance
+    n = 1 << 20
+    dec_period = 64 * 4096
+    gen = bench_c1.Generator(capi, ctx, n, 2)
+    caps = []
+    for k in range(2):
+        d, _ = gen.capture(k, 900 + k)
+        iq = ctx.download(d, np.uint8, 2 * n)
+        d.free()
+        if cw_amp:
+            t = np.arange(n)
+            f = np.where(t < 2 * dec_period + 4096 * 5, 0.1234, -0.31)
+            ph = 2 * np.pi * np.cumsum(f)
+            x = iq.reshape(-1, 2).astype(np.float64) - 128 + cw_amp * np.stack([np.cos(ph), np.sin(ph)], axis=1)
+            iq = np.clip(np.rint(x + 128), 0, 255).astype(np.uint8).reshape(-1)
+        caps.append(iq)
+    gen.close()
+    bufs = [ctx.upload(c) for c in caps]
+    cb = capi.CaptureBatch(ctx, 2, n, bench_c1.OMEGA, anf=anf, tile_len=tile, tile_warmup=512, notch_decimation=dec_period if anf else 0, viterbi=True)
+    try:
+        cb.run_async([b.ptr for b in bufs], n)
+        res = cb.wait()
+        for i in range(2):
+            xf = oracle.cconverter_u8(caps[i])
+            if anf:
+                xf, _ = oracle.auto_notch(xf, 1, dec_period)
+            o = oracle.rx(po.rx_params(sampler=1, cstln=1, omega=bench_c1.OMEGA, meas_decimation=1 << 20, pll_adjustment=1.0 / 6.0), xf)
+            assert res[i]["samples"] == o["consumed"]
+            sym = cb.soft(i, res[i]["symbols"])
+            assert not sym["pad"].any()
+            first = int(512 / bench_c1.OMEGA) - 8
+            rep = tolerance.check_tiled(sym, o["sym"], dict(tiles=res[i]["tiles"], bad_seams=res[i]["seam_bad"], dup=res[i]["seam_dup"], miss=res[i]["seam_miss"]),
+                                        first_exact=first)
+            print(f"anf {anf} tile {tile} capture {i}: {rep}")
+            assert rep["pass"], rep
+    finally:
+        cb.close()
+        for b in bufs:
+            b.free()
+
+
+def _rotate_u8(iq, quarter_turns):
+    a = iq.reshape(-1, 2).copy()
+    for _ in range(quarter_turns % 4):
+        a = np.stack([255 - a[:, 1], a[:, 0]], axis=1)
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def _stage_reference(capi, ctx, soft_ptr, nsym):
+    """What the one-block-per-call C ABI makes of the soft symbols at soft_ptr when the host drives it: a fresh lsdr_viterbi_run, then
+    mpeg_sync (nobody to call next_sync() on) → deinterleaver → rs_decoder → derandomizer.  Returns (bytes, mpeg bytes, TS, stats)."""
+    lib = capi.lib
+    byte_cap = nsym // 4 + 65536
+    pk_cap = byte_cap // 204 + 64
+    vit, msync, derand = capi.Viterbi(ctx, capi.QPSK, capi.FEC12), capi.MpegSync(ctx), capi.Derandomizer(ctx)
+    d_bytes, d_mpeg = ctx.alloc(byte_cap + 64), ctx.alloc(byte_cap + 64)
+    d_rs, d_rts, d_ts = ctx.alloc(pk_cap * 204), ctx.alloc(pk_cap * 188), ctx.alloc(pk_cap * 188)
+    done = bw = 0
+    while True:                                   # (one call takes every chunk that fits; the next one finds nothing)
+        c, p = vit.run_dev(C.c_void_p(soft_ptr + 4 * done), nsym - done, d_bytes.at(bw), byte_cap - bw)
+        if not c:
+            break
+        done += c; bw += p
+    br = mw = 0
+    while True:
+        c3, p3, _, _, _ = msync.run_dev(d_bytes.at(br), bw - br, d_mpeg.at(mw), byte_cap - mw)
+        if not c3 and not p3:
+            break
+        br += c3; mw += p3
+    cons, prod = C.c_size_t(), C.c_size_t()
+    capi.check(lib.lsdr_deinterleaver_run(ctx.h, d_mpeg.ptr, mw, d_rs.ptr, pk_cap, C.byref(cons), C.byref(prod)))
+    npk, n_ts, errs = prod.value, 0, 0
+    if npk:
+        b, e = C.c_long(), C.c_long()
+        capi.check(lib.lsdr_rs_decoder_run(ctx.h, d_rs.ptr, npk, d_rts.ptr, C.byref(b), C.byref(e)))
+        errs = e.value
+        c2, p2 = C.c_size_t(), C.c_size_t()
+        capi.check(lib.lsdr_derandomizer_run(derand.h, d_rts.ptr, npk, d_ts.ptr, pk_cap, C.byref(c2), C.byref(p2)))
+        n_ts = p2.value
+    out = (ctx.download(d_bytes, np.uint8, bw), ctx.download(d_mpeg, np.uint8, mw), ctx.download(d_ts, np.uint8, n_ts * 188),
+           dict(npk=npk, errs=errs, locked=int(msync.locked), sync=int(vit.current_sync)))
+    for d in (d_bytes, d_mpeg, d_rs, d_rts, d_ts):
+        d.free()
+    vit.close(); msync.close(); derand.close()
+    return out
+
+
+def _assert_stages_exact(capi, ctx, cb, res, ts, names):
+    for i, name in enumerate(names):
+        r = res[i]
+        want_bytes, want_mpeg, want_ts, st = _stage_reference(capi, ctx, cb.soft_ptr(i), r["symbols"])
+        got_bytes = cb.stage_bytes(i, "deconv", r["bytes_deconv"])
+        got_mpeg = cb.stage_bytes(i, "mpeg", r["bytes_mpeg"])
+        assert r["bytes_deconv"] == len(want_bytes) and got_bytes.tobytes() == want_bytes.tobytes(), name
+        assert r["alignment"] == st["sync"], (name, r, st)
+        assert r["bytes_mpeg"] == len(want_mpeg) and got_mpeg.tobytes() == want_mpeg.tobytes(), name
+        assert r["rs_packets"] == st["npk"] and r["locked"] == st["locked"] and r["rs_bit_errors"] == st["errs"], (name, r, st)
+        assert r["next_sync_calls"] == 0, (name, r)
+        assert ts[i] == want_ts.tobytes(), name
+        vs = cb.viterbi_stats(i)
+        assert vs["bytes"] == r["bytes_deconv"] and vs["current_sync"] == r["alignment"], (name, vs, r)
+
+
+def test_viterbi_stage_and_tail_are_exact_on_the_objects_own_soft_symbols(capi, ctx):
+    import bench_c1
+    n = 8 << 20
+    gen = bench_c1.Generator(capi, ctx, n, 1)
+    d0, _ = gen.capture(0, 777)
+    gen.close()
+    base = ctx.download(d0, np.uint8, 2 * n)
+    d0.free()
+    rng = np.random.default_rng(5)
+    variants = [("as generated", base)]
+    for q in (1, 2, 3):
+        variants.append((f"rotated {90 * q} deg", _rotate_u8(base, q)))
+    burst = base.copy()
+    burst[2 * (n // 2): 2 * (n // 2 + 300000)] = rng.integers(100, 156, 600000, dtype=np.uint8)
+    variants.append(("garbage burst in the middle", burst))
+    variants.append(("noise only (never locks)", rng.integers(96, 160, 2 * n, dtype=np.uint8).astype(np.uint8)))
+    names = [v[0] for v in variants]
+    bufs = [ctx.upload(v) for _, v in variants]
+    cb = capi.CaptureBatch(ctx, len(variants), n, bench_c1.OMEGA, anf=0, tile_len=2048, tile_warmup=512, viterbi=True)
+    try:
+        res, ts = cb.decode([b.ptr for b in bufs], n)
+        _assert_stages_exact(capi, ctx, cb, res, ts, names)
+        print("rounds:", [cb.viterbi_stats(i) for i in range(len(variants))])
+        assert res[0]["ts_packets"] > 4000 and res[0]["locked"] == 1
+        assert all(res[i]["ts_packets"] > 4000 for i in (1, 2, 3))                    # viterbi_sync's alignment search takes the rotation
+        assert len({res[i]["alignment"] for i in range(4)}) > 1
+        assert 500 < res[4]["ts_packets"] < res[0]["ts_packets"]                      # the burst cost packets, both halves decoded
+        assert res[5]["ts_packets"] == 0 and res[5]["locked"] == 0
+        # a SHORT run on the same object
+        short = base[: 2 * 70000].copy()
+        sb = ctx.upload(short)
+        res2, ts2 = cb.decode([sb.ptr] * len(variants), len(short) // 2)
+        assert all(r["samples"] == (len(short) // 2 - 1) // 128 * 128 for r in res2)
+        assert len(set(ts2)) == 1
+        _assert_stages_exact(capi, ctx, cb, res2[:2], ts2[:2], ["short run, capture 0", "short run, capture 1"])
+        sb.free()
+    finally:
+        cb.close()
+        for b in bufs:
+            b.free()
+
+
+def test_neighbours_do_not_matter(capi, ctx):
+    caps = [_capture(1500, s, n)[0] for s, n in WEAK]
+    n = len(caps[0]) // 2
+    cb4, res4, ts4 = _decode(capi, ctx, caps, n, 0, 4096)
+    st4 = cb4.viterbi_stats(2)
+    cb4.close()
+    cb1, res1, ts1 = _decode(capi, ctx, [caps[2]], n, 0, 4096)
+    st1 = cb1.viterbi_stats(0)
+    cb1.close()
+    assert ts1[0] == ts4[2] and len(ts1[0]) > 1400 * 188
+    assert st1["rounds"] == st4["rounds"] and st1["symbols"] == st4["symbols"] and st1["bytes"] == st4["bytes"], (st1, st4)
+    # the rounds are shared: four copies of a capture take as many as the capture alone
+    cbc, resc, tsc = _decode(capi, ctx, [caps[2]] * 4, n, 0, 4096)
+    try:
+        stc = [cbc.viterbi_stats(i) for i in range(4)]
+        assert all(t == ts1[0] for t in tsc)
+        assert all(s["rounds"] == st1["rounds"] and s["batch_rounds"] == st1["batch_rounds"] for s in stc), (stc, st1)
+    finally:
+        cbc.close()
+
+
+def test_two_partitions_give_the_same_ts(capi, ctx):
+    """aux_cus: the tiles on one compute-unit partition, everything else — Viterbi stage and tail included — on the other."""
+    import bench_c1
+    iq = _capture(1500, 23, 18)[0]
+    n = len(iq) // 2
+    cb0, res0, ts0 = _decode(capi, ctx, [iq, iq], n, 0, 4096)
+    cb0.close()
+    bufs = [ctx.upload(iq) for _ in range(2)]
+    cb = capi.CaptureBatch(ctx, 2, n, bench_c1.OMEGA, anf=0, tile_len=4096, tile_warmup=512, aux_cus=64, viterbi=True)
+    try:
+        for _ in range(2):                                    # (a second batch on the same object)
+            res, ts = cb.decode([b.ptr for b in bufs], n)
+            assert ts == ts0 and len(ts[0]) > 1400 * 188
+            assert [r["symbols"] for r in res] == [r["symbols"] for r in res0]
+    finally:
+        cb.close()
+        for b in bufs:
+            b.free()
