@@ -590,7 +590,9 @@ int lsdr_fastqpsk_run(lsdr_fastqpsk *r, const lsdr_cu8 *in, size_t n_in, uint8_t
                       size_t *produced, float *freq_out_host, size_t freq_cap, size_t *n_freq, lsdr_cu8 *cstln_out_host,
                       size_t cstln_cap, size_t *n_cstln);
 /* dvb_deconvol_sync<u8> (dvb.h:612-707) on deconvol_poly2 (convolutional.h:80-192): 512 hard symbols → 64 bytes per
- * chunk, the four alignments re-scored every resync_period chunks. */
+ * chunk, the four alignments re-scored every resync_period chunks.
+ * Both blocks are one call per buffer with a host read of their counts; the whole `--hs` graph for many captures at once, with every
+ * count on the device, is lsdr_hs_batch (below, behind the capture batch). */
 typedef struct lsdr_hsdeconv lsdr_hsdeconv;
 int lsdr_hsdeconv_create(lsdr_ctx *ctx, int resync_period, lsdr_hsdeconv **d);
 void lsdr_hsdeconv_destroy(lsdr_hsdeconv *d);
@@ -768,6 +770,52 @@ int lsdr_capture_batch_bins(lsdr_capture_batch *b, int i, int *bins, unsigned ca
 int lsdr_capture_batch_notched(lsdr_capture_batch *b, int i, lsdr_cf32 *out_dev, size_t n);
 /* HIP events around the tile kernel of every run while enabled: mean duration since the previous call, then sets the switch */
 int lsdr_capture_batch_tile_time(lsdr_capture_batch *b, int enable, float *avg_ms, unsigned *launches);
+
+/* ------------------------------------------------------------ `--hs` batch
+ * leandvb's "maximum throughput" graph (`leandvb --u8 --hs [--fastlock] [--tune F] [--drift]`, leandvb.cc:813-893) for B independent cu8
+ * captures, each decoded from its FIRST SAMPLE to TS by freshly constructed blocks:
+ *     fast_qpsk_receiver<u8>(omega, set_freq, allow_drift) → dvb_deconvol_sync<u8>(resync_period = fastlock ? 1 : 32) →
+ *     mpeg_sync<u8,0>(deconv = NULL, fastlock = true, resync_period = fastlock ? 1 : 32) → deinterleaver → rs_decoder → derandomizer
+ * (sdr.h:946-1189, dvb.h:612-707, 712-891; rate 1/2 only, no notch).  All captures share every launch (blockIdx.y = capture).  run_async
+ * queues everything on the context's stream and returns — captures uploaded with lsdr_memcpy_h2d on that context are ordered in front of
+ * it; wait is one event synchronisation plus the read of B pinned records.  There are no rounds and no host read in between:
+ *  * receiver: time-tiled as lsdr_fastqpsk_set_tiled does it (one lane per tile, the same seam reconciliation), body symbols staged
+ *    transposed and compacted into one contiguous u8 array per capture, its count in device memory.  Tile 0 runs from the constructed
+ *    state: its symbols are the reference's bit for bit.  Tile j ≥ 1 starts tile_warmup samples early at mu = phase = 0 with the
+ *    CONSTRUCTED frequency word (`freq`) and is held within ± 65536 / omega / 2048 of it (4.07e-4 cycles per sample at omega 1.2) — the
+ *    contract of both tiled receivers: A CAPTURE MUST BE TUNED TO WITHIN THAT WINDOW OF ITS CARRIER (`freq`, leandvb's --tune).
+ *  * dvb_deconvol_sync: all four alignments are scored on the chunks ≡ 0 (mod resync_period); the score uses the second half of a
+ *    chunk's words only, so it carries no history, and for a freshly constructed block the alignment in force while chunk c is decoded is
+ *    c == 0 ? 0 : first arg-min of the scores of chunk ((c − 1) / P)·P — a function of the symbol stream, evaluated per thread.
+ *  * FEC tail: the capture batch's tail without deconvol_sync, mpeg_sync constructed with fastlock / resync_period as above.
+ * lsdr_capture_result as for the capture batch: next_sync_calls is 0, alignment is the deconvolver's alignment at the end, bytes_deconv
+ * is 64 × the chunks decoded, symbols the hard symbols produced, samples = (n_samples − 1) / 128 · 128.
+ * One batch in flight per object: run_async → wait → [ts_download_async → ts_wait]; the next run_async may be queued while a download is
+ * in flight.  LSDR_E_ARG: n_captures < 1, tile sizes that are no multiples of 128, nonzero reserved, n_samples > max_samples, run_async
+ * while a batch is in flight, wait with nothing in flight.  n_samples < 129 is a valid batch that produces nothing.  The accessors
+ * return NULL for i outside [0, n_captures). */
+typedef struct lsdr_hs_batch lsdr_hs_batch;
+typedef struct {
+  int n_captures;            /* B */
+  size_t max_samples;        /* per capture */
+  float omega;               /* Fs/Fm, fast_qpsk_receiver::set_omega */
+  float freq;                /* set_freq(Ftune/Fs), cycles per sample: lsdr_fastqpsk_create's convention */
+  int allow_drift, fastlock;
+  unsigned tile_len, tile_warmup;   /* samples, multiples of 128; 0 = lsdr_fastqpsk_set_tiled's defaults */
+  int reserved[8];           /* 0 */
+} lsdr_hs_batch_cfg;
+int lsdr_hs_batch_create(lsdr_ctx *ctx, const lsdr_hs_batch_cfg *cfg, lsdr_hs_batch **b);
+void lsdr_hs_batch_destroy(lsdr_hs_batch *b);
+/* iq_dev: HOST array of B DEVICE pointers to lsdr_cu8 items (4-byte aligned), n_samples each.  Queues everything; returns at once. */
+int lsdr_hs_batch_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples);
+int lsdr_hs_batch_wait(lsdr_hs_batch *b, lsdr_capture_result *results /* [B], may be NULL */);
+/* after wait: copies every capture's TS (ts_packets·188 bytes) to ts_host[i] (pinned memory recommended) on a side stream */
+int lsdr_hs_batch_ts_download_async(lsdr_hs_batch *b, uint8_t *const *ts_host, size_t cap_bytes);
+int lsdr_hs_batch_ts_wait(lsdr_hs_batch *b);
+const uint8_t *lsdr_hs_batch_ts_dev(const lsdr_hs_batch *b, int i);        /* device buffer of capture i's TS */
+const uint8_t *lsdr_hs_batch_symbols_dev(const lsdr_hs_batch *b, int i);   /* its hard symbols, one per byte (result.symbols of them) */
+const uint8_t *lsdr_hs_batch_bytes_dev(const lsdr_hs_batch *b, int i);     /* dvb_deconvol_sync's output, mpeg_sync's output */
+const uint8_t *lsdr_hs_batch_mpeg_dev(const lsdr_hs_batch *b, int i);
 
 #ifdef __cplusplus
 }

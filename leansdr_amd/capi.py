@@ -332,6 +332,23 @@ _sig("lsdr_capture_batch_bins", C.c_int, [vp, C.c_int, vp, C.c_uint, C.POINTER(C
 _sig("lsdr_capture_batch_notched", C.c_int, [vp, C.c_int, vp, c_sz])
 _sig("lsdr_capture_batch_tile_time", C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint)])
 
+
+class HsBatchCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("max_samples", C.c_size_t), ("omega", C.c_float), ("freq", C.c_float), ("allow_drift", C.c_int),
+                ("fastlock", C.c_int), ("tile_len", C.c_uint), ("tile_warmup", C.c_uint), ("reserved", C.c_int * 8)]
+
+
+_sig("lsdr_hs_batch_create", C.c_int, [vp, C.POINTER(HsBatchCfg), C.POINTER(vp)])
+_sig("lsdr_hs_batch_destroy", None, [vp])
+_sig("lsdr_hs_batch_run_async", C.c_int, [vp, vp, c_sz])
+_sig("lsdr_hs_batch_wait", C.c_int, [vp, vp])
+_sig("lsdr_hs_batch_ts_download_async", C.c_int, [vp, vp, c_sz])
+_sig("lsdr_hs_batch_ts_wait", C.c_int, [vp])
+_sig("lsdr_hs_batch_ts_dev", vp, [vp, C.c_int])
+_sig("lsdr_hs_batch_symbols_dev", vp, [vp, C.c_int])
+_sig("lsdr_hs_batch_bytes_dev", vp, [vp, C.c_int])
+_sig("lsdr_hs_batch_mpeg_dev", vp, [vp, C.c_int])
+
 #: every symbol include/lsdr_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [n for n in dir(lib) if n.startswith("lsdr_")]
 
@@ -935,6 +952,69 @@ class CaptureBatch:
         ms, n = C.c_float(), C.c_uint()
         check(lib.lsdr_capture_batch_tile_time(self.h, 1 if enable else 0, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+class HsBatch:
+    """lsdr_hs_batch: B independent cu8 captures, each from its first sample to TS by leandvb's `--hs` graph (fast_qpsk_receiver →
+    dvb_deconvol_sync → mpeg_sync(fastlock) → deinterleaver → rs_decoder → derandomizer), in shared launches with every count on the
+    device.  freq: the receiver's frequency bias in cycles per sample (FastQpsk's convention)."""
+
+    def __init__(self, ctx, n_captures, max_samples, omega, freq=0.0, allow_drift=0, fastlock=0, tile_len=0, tile_warmup=0):
+        self.ctx, self.n = ctx, int(n_captures)
+        cfg = HsBatchCfg()
+        cfg.n_captures, cfg.max_samples, cfg.omega, cfg.freq = self.n, int(max_samples), omega, freq
+        cfg.allow_drift, cfg.fastlock, cfg.tile_len, cfg.tile_warmup = int(allow_drift), int(fastlock), tile_len, tile_warmup
+        h = vp()
+        check(lib.lsdr_hs_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self._res = (CaptureResult * max(self.n, 1))()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_hs_batch_destroy(self.h)
+            self.h = None
+
+    def run_async(self, iq_ptrs, n_samples):
+        ins = (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs])
+        check(lib.lsdr_hs_batch_run_async(self.h, ins, int(n_samples)))
+
+    def wait(self, results=True):
+        check(lib.lsdr_hs_batch_wait(self.h, self._res if results else None))
+        return [r.as_dict() for r in self._res][:self.n] if results else None
+
+    def ts_download_async(self, host_ptrs, cap_bytes):
+        outs = (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in host_ptrs])
+        check(lib.lsdr_hs_batch_ts_download_async(self.h, outs, int(cap_bytes)))
+
+    def ts_wait(self):
+        check(lib.lsdr_hs_batch_ts_wait(self.h))
+
+    def _fetch(self, ptr, n):
+        a = np.empty(int(n), np.uint8)
+        if n:
+            if ptr is None:
+                raise LsdrError("hs batch: no such capture")
+            check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(a), ptr, int(n)))
+            self.ctx.sync()
+        return a
+
+    def decode(self, iq_ptrs, n_samples):
+        """One batch, synchronously: (results, [TS bytes per capture])."""
+        self.run_async(iq_ptrs, n_samples)
+        res = self.wait()
+        return res, [self._fetch(lib.lsdr_hs_batch_ts_dev(self.h, i), r["ts_packets"] * 188).tobytes() for i, r in enumerate(res)]
+
+    def symbols_ptr(self, i):
+        """Device pointer of capture i's hard symbols, one per byte (None for i out of range)."""
+        return lib.lsdr_hs_batch_symbols_dev(self.h, int(i))
+
+    def symbols(self, i, n):
+        """The first n hard symbols of capture i after a run (host)."""
+        return self._fetch(self.symbols_ptr(i), n)
+
+    def stage_bytes(self, i, which, n):
+        fn = lib.lsdr_hs_batch_bytes_dev if which == "deconv" else lib.lsdr_hs_batch_mpeg_dev
+        return self._fetch(fn(self.h, int(i)), n)
 
 
 def hs2_pack(symbols, offset=0):

@@ -11,6 +11,8 @@
 //                                            before them; the alignment in force after a resync chunk is the
 //                                            arg-min of the four error counts of that chunk (independent of the
 //                                            previous one) → two fully parallel kernels.
+//   lsdr_hs_batch           leandvb.cc:813-893 the whole `--hs` graph for B captures in shared launches, nothing read back in between
+//                                            (hsb_device.h / hsb_host.h; the FEC tail is fec.hip's lsdr_tail)
 //
 // Tables are built on the host with the reference's libm expressions (host_tables.cpp) and uploaded once.
 #include "lsdr_internal.h"
@@ -381,6 +383,8 @@ __global__ __launch_bounds__(256) void k_hsd_decode(hsd_args a) {
   po[0] = (unsigned char)(wd >> 24); po[1] = (unsigned char)(wd >> 16); po[2] = (unsigned char)(wd >> 8); po[3] = (unsigned char)wd;
 }
 
+#include "hsb_device.h"      // lsdr_hs_batch: both blocks for many captures in shared launches
+
 }  // namespace
 
 struct lsdr_fastqpsk {
@@ -736,3 +740,5 @@ int lsdr_hsdeconv_run(lsdr_hsdeconv *d, const uint8_t *in, size_t n_in, uint8_t 
 }
 
 }  // extern "C"
+
+#include "hsb_host.h"       // lsdr_hs_batch

@@ -127,6 +127,12 @@ const uint8_t *lsdr_tail_ts_dev(const lsdr_tail *t, unsigned i);
 size_t lsdr_tail_ts_cap(const lsdr_tail *t);
 const uint8_t *lsdr_tail_bytes_dev(const lsdr_tail *t, unsigned i);
 const uint8_t *lsdr_tail_mpeg_dev(const lsdr_tail *t, unsigned i);
+// the tail without deconvol_sync (nodeconv) behind a producer that stays on the device (hs.hip's lsdr_hs_batch): mpeg_sync's public members
+// fastlock / resync_period (dvb.h:716-717) as every capture's block is constructed, and the [n] device records {bytes, alignment} that
+// k_tail_acquire_bytes reads — written by the producer's last kernel instead of lsdr_tail_set_bytes
+struct lsdr_tail_vit { unsigned long long bytes; unsigned alignment, pad; };   // = tail_device.h's tail_vit
+int lsdr_tail_set_mpeg_sync(lsdr_tail *t, int fastlock, int resync_period);
+lsdr_tail_vit *lsdr_tail_vit_dev(lsdr_tail *t);
 
 // Host-side table builders (host_tables.cpp)
 namespace lsdr {

@@ -125,6 +125,13 @@ int lsdr_tail_set_bytes(lsdr_tail *t, const unsigned long long *bytes, const uns
   return LSDR_OK;
 }
 
+int lsdr_tail_set_mpeg_sync(lsdr_tail *t, int fastlock, int resync_period) {
+  LSDR_ARG(t && resync_period >= 1);
+  t->A.ms0.fastlock = fastlock ? 1 : 0; t->A.ms0.resync_period = resync_period;
+  return LSDR_OK;
+}
+lsdr_tail_vit *lsdr_tail_vit_dev(lsdr_tail *t) { return t && t->nodeconv ? reinterpret_cast<lsdr_tail_vit *>(t->d_vit) : nullptr; }
+
 int lsdr_tail_launch(lsdr_tail *t, hipEvent_t before_ts) {
   LSDR_ARG(t);
   lsdr_ctx *c = t->ctx;
@@ -162,5 +169,7 @@ const uint8_t *lsdr_tail_bytes_dev(const lsdr_tail *t, unsigned i) { return t &&
 const uint8_t *lsdr_tail_mpeg_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].mpeg : nullptr; }
 
 static_assert(sizeof(lsdr_tail_result) == sizeof(tail_result), "lsdr_internal.h mirrors tail_device.h's result record");
+static_assert(sizeof(lsdr_tail_vit) == sizeof(tail_vit) && offsetof(lsdr_tail_vit, alignment) == offsetof(tail_vit, alignment),
+              "lsdr_internal.h mirrors tail_device.h's tail_vit");
 
 #endif  // LSDR_TAIL_HOST_H
