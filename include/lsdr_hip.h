@@ -771,9 +771,46 @@ int lsdr_capture_batch_notched(lsdr_capture_batch *b, int i, lsdr_cf32 *out_dev,
 /* HIP events around the tile kernel of every run while enabled: mean duration since the previous call, then sets the switch */
 int lsdr_capture_batch_tile_time(lsdr_capture_batch *b, int enable, float *avg_ms, unsigned *launches);
 
+/* Other sample formats: the same object for captures that are not cu8.  leandvb reads five formats into the same graph (leandvb.cc:208-261);
+ * here the format replaces the graph's first block(s), fused into every load that touches a capture — the converted, scaled stream never
+ * exists in device memory:
+ *     LSDR_IN_CU8   --u8   cconverter<u8,128,f32,0,1,1>         leandvb.cc:211-217   (the default; exactly lsdr_capture_batch_create[_viterbi])
+ *     LSDR_IN_CS8   --s8   cconverter<s8,0,f32,0,1,1>           leandvb.cc:218-227
+ *     LSDR_IN_CU16  --u16  cconverter<u16,32768,f32,0,1,1>      leandvb.cc:228-237
+ *     LSDR_IN_CS16  --s16  cconverter<s16,0,f32,0,1,1>          leandvb.cc:238-248
+ *     LSDR_IN_CF32  --f32 --float-scale in_scale                leandvb.cc:249-258: the raw items through scaler<float,cf32,cf32>
+ * (dsp.h:40-50: float((int)item − Z), exact for all four integer types; dsp.h:149-156: re·scale, im·scale, one rounding each).  in_scale
+ * behind an integer format is that scaler behind the converter — a block leandvb does not put there; it exists for the LEVEL CONTRACT:
+ * tiles j ≥ 1 start from the constructed AGC (est_insp = 75², gain 1) and cannot re-measure the level in their warm-up (kest = 0.01 per
+ * chunk), so THE CONVERTED, SCALED SAMPLES MUST HAVE AN RMS NEAR 75, which cu8 data has by construction and 16-bit or float data only if the
+ * caller scales it (a power of two where bit-identity with another format matters: s16 = 256·s8 with in_scale 2^-8 is the s8 run bit for
+ * bit).  Measured window (profiles/capture_batch_formats/level.txt: true 16-bit captures against `leandvb --f32 --float-scale` at the same
+ * value): RMS 19 … 75 — the TS is the reference's, at noise 7.5 (both engines) and at noise 18 (Viterbi engine); RMS 150 — still at noise 7.5,
+ * the weak capture loses 14 % of its packets; RMS 300 — the weak capture does not lock (seam_bad > 0).  When in doubt scale low.  Tile 0 is the reference's arithmetic
+ * on the converted floats bit for bit, the detect FFT likewise; the rest is the tolerance class of the cu8 object.
+ * Every other lsdr_capture_batch_* call works on an object made this way, except the typed lsdr_capture_batch_run_async, which returns
+ * LSDR_E_ARG on a non-cu8 object (a cu8 pointer is never read as wider items).  All captures of a batch have the object's format.
+ * LSDR_E_ARG: in_format outside the five, in_scale negative or not finite, nonzero reserved, a capture pointer not aligned to its item
+ * size (2, 2, 4, 4, 8 bytes; 16 with anf = 1).  LSDR_E_UNSUPPORTED: LSDR_IN_CU8 with a scale other than 0 or 1 (the cu8 kernels have no
+ * scaler); for the other formats max_samples × bytes per item ≥ 0xfff00000 (the tiles' 32-bit buffer offsets: 2^30 samples of a 16-bit
+ * format, 2^29 of cf32, are too many). */
+typedef struct {
+  int in_format;     /* LSDR_IN_CU8 (default), LSDR_IN_CS8, LSDR_IN_CU16, LSDR_IN_CS16: cconverter<T,Z,f32,0,1,1> (leandvb.cc:208-248, dsp.h:40-50);
+                        LSDR_IN_CF32: the raw cf32 items (leandvb.cc:249-258) */
+  float in_scale;    /* 0 or 1: none.  Else every converted sample is multiplied by it, re and im, one rounding each: scaler<float,cf32,cf32>
+                        (dsp.h:149-156) behind the converter; for cf32 it IS leandvb's --float-scale */
+  int reserved[6];   /* 0 */
+} lsdr_capture_input_cfg;
+/* vcfg == NULL: the default engine; icfg == NULL: cu8, unscaled (then exactly lsdr_capture_batch_create[_viterbi]) */
+int lsdr_capture_any_create(lsdr_ctx *ctx, const lsdr_capture_batch_cfg *cfg, const lsdr_capture_viterbi_cfg *vcfg,
+                            const lsdr_capture_input_cfg *icfg, lsdr_capture_batch **b);
+/* iq_dev: HOST array of B DEVICE pointers to n_samples items of the object's format, aligned to the item size (16 bytes with anf = 1) */
+int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev, size_t n_samples);
+
 /* ------------------------------------------------------------ `--hs` batch
  * leandvb's "maximum throughput" graph (`leandvb --u8 --hs [--fastlock] [--tune F] [--drift]`, leandvb.cc:813-893) for B independent cu8
- * captures, each decoded from its FIRST SAMPLE to TS by freshly constructed blocks:
+ * captures, each decoded from its FIRST SAMPLE to TS by freshly constructed blocks (cu8 only, and it stays so: `--hs requires --u8`,
+ * leandvb.cc:773-774 — the other sample formats are lsdr_capture_any_create's):
  *     fast_qpsk_receiver<u8>(omega, set_freq, allow_drift) → dvb_deconvol_sync<u8>(resync_period = fastlock ? 1 : 32) →
  *     mpeg_sync<u8,0>(deconv = NULL, fastlock = true, resync_period = fastlock ? 1 : 32) → deinterleaver → rs_decoder → derandomizer
  * (sdr.h:946-1189, dvb.h:612-707, 712-891; rate 1/2 only, no notch).  All captures share every launch (blockIdx.y = capture).  run_async

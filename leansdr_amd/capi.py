@@ -22,6 +22,7 @@ SOFTSYM = np.dtype([("cost", "<i2"), ("symbol", "u1"), ("pad", "u1")])
 CSTLN_BITS = {BPSK: 1, QPSK: 2, PSK8: 3, APSK16: 4, APSK32: 5, APSK64E: 6, QAM16: 4, QAM64: 6, QAM256: 8}
 (FEC12, FEC23, FEC46, FEC34, FEC56, FEC78, FEC45, FEC89, FEC910) = range(9)
 IN_CF32, IN_CU8 = 0, 1
+IN_CS8, IN_CU16, IN_CS16 = 2, 3, 4
 SYM_SOFT, SYM_HARD2 = 0, 1
 FIR_EXACT, FIR_FMA, FIR_MFMA, FIR_MFMA_BLK = 0, 1, 2, 3
 SAMP_NEAREST, SAMP_LINEAR, SAMP_FIR = 0, 1, 2
@@ -317,6 +318,12 @@ class CaptureViterbiStats(C.Structure):
 
 _sig("lsdr_capture_batch_create", C.c_int, [vp, C.POINTER(CaptureBatchCfg), C.POINTER(vp)])
 _sig("lsdr_capture_batch_create_viterbi", C.c_int, [vp, C.POINTER(CaptureBatchCfg), C.POINTER(CaptureViterbiCfg), C.POINTER(vp)])
+class CaptureInputCfg(C.Structure):
+    _fields_ = [("in_format", C.c_int), ("in_scale", C.c_float), ("reserved", C.c_int * 6)]
+
+
+_sig("lsdr_capture_any_create", C.c_int, [vp, C.POINTER(CaptureBatchCfg), C.POINTER(CaptureViterbiCfg), C.POINTER(CaptureInputCfg), C.POINTER(vp)])
+_sig("lsdr_capture_any_run_async", C.c_int, [vp, vp, c_sz])
 _sig("lsdr_capture_batch_soft_dev", vp, [vp, C.c_int])
 _sig("lsdr_capture_batch_viterbi_stats", C.c_int, [vp, C.c_int, C.POINTER(CaptureViterbiStats)])
 _sig("lsdr_capture_batch_destroy", None, [vp])
@@ -841,10 +848,12 @@ class RxBatch:
 class CaptureBatch:
     """lsdr_capture_batch: B independent cu8 captures, each from its first sample to TS (leandvb's default `--u8` graph per capture),
     in shared launches with the counts on the device.  viterbi=True (or a dict of lsdr_capture_viterbi_cfg fields): the `--viterbi` graph —
-    soft symbols, viterbi_sync, mpeg_sync without a deconvolver."""
+    soft symbols, viterbi_sync, mpeg_sync without a deconvolver.  in_format / in_scale (lsdr_capture_input_cfg): captures of IN_CS8,
+    IN_CU16, IN_CS16 or IN_CF32 items, converted (and multiplied by in_scale) in the kernels' loads — leandvb's --s8 / --u16 / --s16 /
+    --f32 --float-scale; the converted samples must have an RMS near 75 (the level contract, include/lsdr_hip.h)."""
 
     def __init__(self, ctx, n_captures, max_samples, omega, fec=FEC12, anf=1, tile_len=0, tile_warmup=0, notch_k=0.0, notch_decimation=0,
-                 unlocked_window=0, aux_cus=0, viterbi=None):
+                 unlocked_window=0, aux_cus=0, viterbi=None, in_format=IN_CU8, in_scale=0.0):
         self.ctx, self.n = ctx, int(n_captures)
         cfg = CaptureBatchCfg()
         cfg.n_captures, cfg.max_samples, cfg.omega, cfg.fec, cfg.anf = self.n, int(max_samples), omega, fec, anf
@@ -854,9 +863,16 @@ class CaptureBatch:
         self.unlocked_window = unlocked_window or 8192
         h = vp()
         self.viterbi = bool(viterbi)
+        self.in_format, self.in_scale = int(in_format), float(in_scale)
+        self._any = self.in_format != IN_CU8 or self.in_scale != 0.0
+        vcfg = CaptureViterbiCfg()
         if self.viterbi:
-            vcfg = CaptureViterbiCfg()
             vcfg.resync_period = int(viterbi.get("resync_period", 0)) if isinstance(viterbi, dict) else 0
+        if self._any:
+            icfg = CaptureInputCfg()
+            icfg.in_format, icfg.in_scale = self.in_format, self.in_scale
+            check(lib.lsdr_capture_any_create(ctx.h, C.byref(cfg), C.byref(vcfg) if self.viterbi else None, C.byref(icfg), C.byref(h)))
+        elif self.viterbi:
             check(lib.lsdr_capture_batch_create_viterbi(ctx.h, C.byref(cfg), C.byref(vcfg), C.byref(h)))
         else:
             check(lib.lsdr_capture_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
@@ -870,7 +886,10 @@ class CaptureBatch:
 
     def run_async(self, iq_ptrs, n_samples):
         ins = (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs])
-        check(lib.lsdr_capture_batch_run_async(self.h, ins, int(n_samples)))
+        if self._any:
+            check(lib.lsdr_capture_any_run_async(self.h, ins, int(n_samples)))
+        else:
+            check(lib.lsdr_capture_batch_run_async(self.h, ins, int(n_samples)))
 
     def wait(self, results=True):
         check(lib.lsdr_capture_batch_wait(self.h, self._res if results else None))

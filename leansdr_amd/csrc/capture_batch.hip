@@ -9,6 +9,9 @@
 // lsdr_viterbi_batch commits a prefix per call, so a batch takes several ROUNDS: run_async queues the front end and round 1 (symbol counts
 // from device memory), wait drives the remaining rounds — one host read of B records each, every round shared by all captures — and then
 // queues the tail.
+//
+// Other sample formats (lsdr_capture_any_create): `leandvb --s8 / --u16 / --s16 / --f32 --float-scale S` (leandvb.cc:208-261) in place of
+// `--u8`.  Format and scale only select the front end's kernels (rxb_device.h converts in its loads); everything here is format-blind.
 #include "lsdr_internal.h"
 
 struct lsdr_capture_batch {
@@ -27,6 +30,7 @@ struct lsdr_capture_batch {
   lsdr_viterbi_batch *vb;
   size_t soft_cap, byte_cap;
   std::vector<lsdr_capture_viterbi_stats> vstats;
+  int in_format; float in_scale;   // lsdr_capture_input_cfg (cu8, 0 by default)
 };
 
 // one more round of the Viterbi stage: stream i continues behind what it has committed.  first: the symbol counts are still on the device.
@@ -81,6 +85,15 @@ static int capture_batch_partition(lsdr_capture_batch *b, lsdr_ctx *caller) {
 }
 
 static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi_cfg *vcfg) {
+  {
+    // the input format is refused before anything is allocated (lsdr_rxb_create_in repeats the checks with their messages)
+    const int f = b->in_format;
+    LSDR_ARG(f == LSDR_IN_CU8 || f == LSDR_IN_CS8 || f == LSDR_IN_CU16 || f == LSDR_IN_CS16 || f == LSDR_IN_CF32);
+    LSDR_ARG(b->in_scale >= 0.f && !std::isinf(b->in_scale));
+    if (f == LSDR_IN_CU8 && b->in_scale != 0.f && b->in_scale != 1.0f) {
+      lsdr_set_error("capture_batch: cu8 captures take no in_scale (got %g): the cu8 kernels have no scaler", (double)b->in_scale); return LSDR_E_UNSUPPORTED;
+    }
+  }
   LSDR_HIP(hipSetDevice(b->ctx->device));
   lsdr_ctx *const caller = b->ctx;
   int vrate = b->cfg.fec;
@@ -98,7 +111,7 @@ static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi
   const unsigned window = b->cfg.unlocked_window ? b->cfg.unlocked_window : 8192u;
   size_t stride = 0;
   if (vcfg) {
-    LSDR_TRY(lsdr_rxb_create_ex(c, &b->cfg, 1, 1.0f / 6.0f, &b->rx));   // cstln_receiver::pll_adjustment behind viterbi_sync, leandvb.cc:498-501
+    LSDR_TRY(lsdr_rxb_create_in(c, &b->cfg, 1, 1.0f / 6.0f, b->in_format, b->in_scale, &b->rx));   // cstln_receiver::pll_adjustment behind viterbi_sync, leandvb.cc:498-501
     b->soft_cap = lsdr_rxb_soft_cap(b->rx);
     LSDR_TRY(lsdr_viterbi_batch_create(ct, LSDR_QPSK, vrate, b->cfg.n_captures, b->soft_cap, &b->vb));
     if (vcfg->resync_period > 0) LSDR_TRY(lsdr_viterbi_batch_set_resync_period(b->vb, vcfg->resync_period));
@@ -111,7 +124,7 @@ static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi
     memset(&z, 0, sizeof(z));
     b->vstats.assign(b->cfg.n_captures, z);
   } else {
-    LSDR_TRY(lsdr_rxb_create(c, &b->cfg, &b->rx));
+    LSDR_TRY(lsdr_rxb_create_in(c, &b->cfg, 0, 1.0f, b->in_format, b->in_scale, &b->rx));
     const size_t sym_cap = lsdr_rxb_words_cap(b->rx) * 16;
     LSDR_TRY(lsdr_tail_create(ct, (unsigned)b->cfg.n_captures, sym_cap, b->cfg.fec, window, &b->tail));
     std::vector<const uint32_t *> words(b->cfg.n_captures);
@@ -126,34 +139,40 @@ static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi
   return LSDR_OK;
 }
 
-int lsdr_capture_batch_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_capture_batch **out) {
-  LSDR_ARG(c && cfg && out);
-  lsdr_capture_batch *b = new lsdr_capture_batch();
-  b->ctx = c; b->cfg = *cfg;
-  const int rc = capture_batch_build(b, nullptr);
-  if (rc) { lsdr_capture_batch_destroy(b); return rc; }
-  *out = b;
-  return LSDR_OK;
-}
-
-int lsdr_capture_batch_create_viterbi(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, const lsdr_capture_viterbi_cfg *vcfg, lsdr_capture_batch **out) {
+int lsdr_capture_any_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, const lsdr_capture_viterbi_cfg *vcfg, const lsdr_capture_input_cfg *icfg,
+                            lsdr_capture_batch **out) {
   LSDR_ARG(c && cfg && out);
   lsdr_capture_viterbi_cfg v;
   memset(&v, 0, sizeof(v));
   if (vcfg) v = *vcfg;
+  int in_format = LSDR_IN_CU8; float in_scale = 0.f;
+  if (icfg) {
+    for (int i = 0; i < 6; ++i) LSDR_ARG(icfg->reserved[i] == 0);
+    in_format = icfg->in_format; in_scale = icfg->in_scale;
+  }
   lsdr_capture_batch *b = new lsdr_capture_batch();
-  b->ctx = c; b->cfg = *cfg;
-  const int rc = capture_batch_build(b, &v);
+  b->ctx = c; b->cfg = *cfg; b->in_format = in_format; b->in_scale = in_scale;
+  const int rc = capture_batch_build(b, vcfg ? &v : nullptr);
   if (rc) { lsdr_capture_batch_destroy(b); return rc; }
   *out = b;
   return LSDR_OK;
 }
 
-int lsdr_capture_batch_run_async(lsdr_capture_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples) {
+int lsdr_capture_batch_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_capture_batch **out) {
+  return lsdr_capture_any_create(c, cfg, nullptr, nullptr, out);
+}
+
+int lsdr_capture_batch_create_viterbi(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, const lsdr_capture_viterbi_cfg *vcfg, lsdr_capture_batch **out) {
+  lsdr_capture_viterbi_cfg v;
+  memset(&v, 0, sizeof(v));
+  return lsdr_capture_any_create(c, cfg, vcfg ? vcfg : &v, nullptr, out);
+}
+
+int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev, size_t n_samples) {
   LSDR_ARG(b && iq_dev);
   if (b->in_flight) { lsdr_set_error("capture_batch: a batch is in flight (lsdr_capture_batch_wait first)"); return LSDR_E_ARG; }
   if (b->vb) LSDR_TRY(lsdr_viterbi_batch_reset(b->vb, -1));              // every capture: a freshly constructed viterbi_sync
-  LSDR_TRY(lsdr_rxb_launch(b->rx, reinterpret_cast<const void *const *>(iq_dev), n_samples, &b->consumed, b->ctx_aux ? b->ctx_aux->stream : nullptr));
+  LSDR_TRY(lsdr_rxb_launch(b->rx, iq_dev, n_samples, &b->consumed, b->ctx_aux ? b->ctx_aux->stream : nullptr));
   if (b->vb) {
     const std::vector<unsigned long long> zero(b->cfg.n_captures, 0ull);
     LSDR_TRY(capture_batch_viterbi_round(b, true, zero, zero, zero));
@@ -164,6 +183,14 @@ int lsdr_capture_batch_run_async(lsdr_capture_batch *b, const lsdr_cu8 *const *i
   LSDR_HIP(hipEventRecord(b->ev_done, (b->ctx_aux ? b->ctx_aux : b->ctx)->stream));
   b->in_flight = true; b->waited = false;
   return LSDR_OK;
+}
+
+int lsdr_capture_batch_run_async(lsdr_capture_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples) {
+  LSDR_ARG(b && iq_dev);
+  if (b->in_format != LSDR_IN_CU8) {                                     // (a cu8 pointer is never read as wider items)
+    lsdr_set_error("capture_batch: this object reads in_format %d: lsdr_capture_any_run_async", b->in_format); return LSDR_E_ARG;
+  }
+  return lsdr_capture_any_run_async(b, reinterpret_cast<const void *const *>(iq_dev), n_samples);
 }
 
 int lsdr_capture_batch_wait(lsdr_capture_batch *b, lsdr_capture_result *results) {

@@ -128,6 +128,37 @@ template <> struct in_stream<LSDR_IN_CU8> { typedef in_cu8 type; };
 template <int FMT> __device__ __forceinline__ typename in_stream<FMT>::type in_make(const void *p) {
   typename in_stream<FMT>::type r; r.p = reinterpret_cast<decltype(r.p)>(p); return r;
 }
+// The capture batch's other input formats (lsdr_capture_input_cfg; tile 0 of rxb_device.h reads through these): the integer items of
+// cconverter<T,Z,f32,0,1,1> (leandvb.cc:208-248; dsp.h:40-50: (int)in − Z, then → float, exact for 8- and 16-bit items) or the raw cf32
+// items (leandvb.cc:249-258), each followed by scaler<float,cf32,cf32> (dsp.h:149-156): re·scale, im·scale, one rounding each (scale 1
+// is the identity, bit for bit).  Internal format numbers: one per item size, the 16-bit bias (cu16: 32768, cs16: 0) as an xor mask.
+enum { kInS8 = 32, kIn16 = 33, kInF32S = 34 };
+struct in_s8s {
+  const char2 *p; float scale;
+  __device__ __forceinline__ float2 operator[](long long i) const { const char2 v = p[i]; return make_float2((float)(int)v.x * scale, (float)(int)v.y * scale); }
+  __device__ __forceinline__ in_s8s operator+(long long k) const { in_s8s r = *this; r.p = p + k; return r; }
+};
+struct in_16s {
+  const unsigned *p; float scale; unsigned flip;          // flip = 0x80008000 for cu16: u16 − 32768 = the item with its top bit flipped, as s16
+  __device__ __forceinline__ float2 operator[](long long i) const {
+    const unsigned v = p[i] ^ flip;
+    return make_float2((float)(int)(short)(v & 0xffffu) * scale, (float)((int)v >> 16) * scale);
+  }
+  __device__ __forceinline__ in_16s operator+(long long k) const { in_16s r = *this; r.p = p + k; return r; }
+};
+struct in_cf32s {
+  const float2 *p; float scale;
+  __device__ __forceinline__ float2 operator[](long long i) const { const float2 v = p[i]; return make_float2(v.x * scale, v.y * scale); }
+  __device__ __forceinline__ in_cf32s operator+(long long k) const { in_cf32s r = *this; r.p = p + k; return r; }
+};
+template <> struct in_stream<kInS8> { typedef in_s8s type; };
+template <> struct in_stream<kIn16> { typedef in_16s type; };
+template <> struct in_stream<kInF32S> { typedef in_cf32s type; };
+__device__ __forceinline__ void in_conv(in_cf32 &, float, unsigned) {}
+__device__ __forceinline__ void in_conv(in_cu8 &, float, unsigned) {}
+__device__ __forceinline__ void in_conv(in_s8s &s, float scale, unsigned) { s.scale = scale; }
+__device__ __forceinline__ void in_conv(in_16s &s, float scale, unsigned flip) { s.scale = scale; s.flip = flip; }
+__device__ __forceinline__ void in_conv(in_cf32s &s, float scale, unsigned) { s.scale = scale; }
 
 // The tolerance tiles' look-ahead window: the samples the NEXT symbol can need (instant n' = n + ⌊mu + omega + mucorr⌋ is one
 // of two adjacent positions, the linear sampler reads n' and n'+1), requested one symbol step ahead.
@@ -612,8 +643,9 @@ __device__ __forceinline__ void rx_tile_meas(const rx_tiled_args &a, unsigned lo
 // SOFT_T (with HARD, the capture batch's soft tiles: rxb_device.h): the packed tails for the seam vote as with HARD, but the body as whole
 // soft symbols in the transposed layout, symbol k at a.stage[k·a.hpitch].
 template <int SAMP, int FMT, bool HARD, bool SOFT_T = false>
-__device__ __forceinline__ void rx_tile_exact(const rx_tiled_args &a) {
-  const typename in_stream<FMT>::type src = in_make<FMT>(a.in);
+__device__ __forceinline__ void rx_tile_exact(const rx_tiled_args &a, float in_scale = 1.0f, unsigned in_flip = 0u) {
+  typename in_stream<FMT>::type src = in_make<FMT>(a.in);
+  in_conv(src, in_scale, in_flip);                      // (the capture batch's converted formats only)
   unsigned long long c1 = a.first_chunks;
   if (c1 > a.total_chunks) c1 = a.total_chunks;
   rx_state_dev s = *a.state;

@@ -1,6 +1,7 @@
 // leansdr_amd/csrc/hsb_device.h — device side of lsdr_hs_batch (include/lsdr_hip.h): leandvb's `--hs` graph for B independent cu8 captures in
 // shared launches (included inside hs.hip's anonymous namespace, behind fq_chunk / hs_word / rx_tiling.h).  blockIdx.y = capture everywhere;
-// every capture starts from the constructed state, so no state is carried and nothing is read back between the kernels:
+// every capture starts from the constructed state, so no state is carried and nothing is read back between the kernels.  cu8 only, and it
+// stays so: `--hs requires --u8` in the reference too (leandvb.cc:773-774); the other sample formats belong to lsdr_capture_any_create.
 //
 //   k_hsb_reset     clears the per-capture records (a second batch sees nothing of the first)
 //   k_hsb_tiles     fast_qpsk_receiver<u8> time-tiled, one lane per tile, fq_chunk's arithmetic.  Tile 0 (a block of its own) runs the

@@ -94,6 +94,8 @@ int lsdr_fir_stream_iv_launch(lsdr_ctx *c, const void *in, size_t n_in, lsdr_cf3
 struct lsdr_rxb;
 int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **out);
 int lsdr_rxb_create_ex(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, lsdr_rxb **out);
+int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, int in_format, float in_scale, lsdr_rxb **out);
+int lsdr_rxb_in_format(const lsdr_rxb *b);
 void lsdr_rxb_destroy(lsdr_rxb *b);
 int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t *consumed, hipStream_t aux = nullptr);
 const uint32_t *lsdr_rxb_words(const lsdr_rxb *b, unsigned i);

@@ -8,6 +8,8 @@
 //                        p = (1−k)·exp(j2π·bin/4096) and whether the estimator restarts there (sdr.h:94-103: only when the bin changes)
 //   k_rxb_notch_pre      zero-start sums of the estimator recurrence over blocks of `pre_block` samples: a tile that starts in the
 //                        middle of a capture gets its estimator from the few blocks in front of it ((1−k)^8192 < 1e-7)
+//   (every kernel that reads a capture is instantiated per sample format — "sample formats" below: cu8 as it always was; cs8, cu16 / cs16
+//    and cf32 with scaler's factor for lsdr_capture_any_create: leandvb --s8 / --u16 / --s16 / --f32 --float-scale, leandvb.cc:208-261)
 //   k_rxb_tiles<NOTCH>   the tolerance tiles (one lane per tile, 64 consecutive tiles of one capture per wavefront, cu8 samples staged
 //                        through LDS by buffer→LDS loads), packed 2-bit decisions out (rx_tiling.h "hs2")
 //   k_rxb_seam / k_rxb_compact   rx_tiling.h's seam pass and packed compaction, blockIdx.y = capture
@@ -68,15 +70,69 @@ struct rxb_args {
   float nk, l2omk;                     // auto_notch::k, log2(1 − k)
   rx_consts C;
   rx_tables T;
+  float in_scale;                      // the converted formats (rxb_in below): scaler's factor (1: none), the 16-bit items' bias as an xor mask
+  unsigned in_flip;
+};
+
+// ---- sample formats ----------------------------------------------------------------------------------------------------------------
+// Every kernel that reads a capture converts in its loads: value = float(item − Z)·in_scale (cconverter<T,Z,f32,0,1,1>, dsp.h:40-50, exact;
+// then scaler<float,cf32,cf32>, dsp.h:149-156, one rounding per component; in_scale = 1 is the identity).  One KIND per item size:
+//   kRxbU8   cu8, no scale: the kernels of the cu8 objects, untouched (leandvb --u8, leandvb.cc:211-217)
+//   kRxbS8   cs8 (--s8, leandvb.cc:218-227)
+//   kRxb16   cu16 / cs16 (--u16 / --s16, leandvb.cc:228-248): the bias 32768 is the item's top bit, flipped by in_flip = 0x80008000
+//   kRxbF32  cf32 (--f32 --float-scale, leandvb.cc:249-258)
+// kStage is the tile kernel's LDS stage length in samples (rxb_stage).
+enum { kRxbU8 = 0, kRxbS8 = 1, kRxb16 = 2, kRxbF32 = 3 };
+__device__ __forceinline__ float rxb_u8f(unsigned w, int byte) {       // (float)((int)u8 − 128): flip the top bit, sign-extend
+  return (float)(int)(signed char)((w ^ 0x8080u) >> (8 * byte));
+}
+__device__ __forceinline__ unsigned rxb_word(unsigned w) { return w; }
+__device__ __forceinline__ unsigned rxb_word(const float2 &) { return 0u; }
+template <int K> struct rxb_in;
+template <> struct rxb_in<kRxbU8> {
+  typedef unsigned item;
+  static constexpr int kBytes = 2, kStage = 32, kTile0 = LSDR_IN_CU8;
+  static __device__ __forceinline__ item ld(const void *p) { return *reinterpret_cast<const unsigned short *>(p); }
+  static __device__ __forceinline__ float re(item w, float, unsigned) { return rxb_u8f(w, 0); }
+  static __device__ __forceinline__ float im(item w, float, unsigned) { return rxb_u8f(w, 1); }
+};
+template <> struct rxb_in<kRxbS8> {
+  typedef unsigned item;
+  static constexpr int kBytes = 2, kStage = 32, kTile0 = kInS8;
+  static __device__ __forceinline__ item ld(const void *p) { return *reinterpret_cast<const unsigned short *>(p); }
+  static __device__ __forceinline__ float re(item w, float sc, unsigned) { return (float)(int)(signed char)w * sc; }
+  static __device__ __forceinline__ float im(item w, float sc, unsigned) { return (float)(int)(signed char)(w >> 8) * sc; }
+};
+template <> struct rxb_in<kRxb16> {
+  typedef unsigned item;
+  static constexpr int kBytes = 4, kStage = 8, kTile0 = kIn16;
+  static __device__ __forceinline__ item ld(const void *p) { return *reinterpret_cast<const unsigned *>(p); }
+  static __device__ __forceinline__ float re(item w, float sc, unsigned flip) { return (float)(int)(short)((w ^ flip) & 0xffffu) * sc; }
+  static __device__ __forceinline__ float im(item w, float sc, unsigned flip) { return (float)((int)(w ^ flip) >> 16) * sc; }
+};
+template <> struct rxb_in<kRxbF32> {
+  typedef float2 item;
+  static constexpr int kBytes = 8, kStage = 8, kTile0 = kInF32S;
+  static __device__ __forceinline__ item ld(const void *p) { return *reinterpret_cast<const float2 *>(p); }
+  static __device__ __forceinline__ float re(item w, float sc, unsigned) { return w.x * sc; }
+  static __device__ __forceinline__ float im(item w, float sc, unsigned) { return w.y * sc; }
 };
 
 // ---- detect chain ----------------------------------------------------------------------------------------------------------------
+template <int K>
 __global__ __launch_bounds__(256) void k_rxb_detect_fft(rxb_args A) {
+  typedef rxb_in<K> IN;
   const rxb_cap &cap = A.caps[blockIdx.y];
   if ((blockIdx.x >> 1) >= cap.n_det) return;
-  const unsigned char *src = cap.in + 2ull * kDetN * A.det_block[blockIdx.x >> 1];
-  cfft_half_body_t([&](unsigned i) { const uchar2 v = reinterpret_cast<const uchar2 *>(src)[i]; return cu8_to_cf32(v.x, v.y); }, A.om, cap.halves,
-                   blockIdx.x);
+  const unsigned char *src = cap.in + (unsigned long long)IN::kBytes * kDetN * A.det_block[blockIdx.x >> 1];
+  if constexpr (K == kRxbU8)
+    cfft_half_body_t([&](unsigned i) { const uchar2 v = reinterpret_cast<const uchar2 *>(src)[i]; return cu8_to_cf32(v.x, v.y); }, A.om, cap.halves,
+                     blockIdx.x);
+  else {
+    const float sc = A.in_scale; const unsigned flip = A.in_flip;
+    cfft_half_body_t([&](unsigned i) { const typename IN::item w = IN::ld(src + (size_t)IN::kBytes * i); return make_float2(IN::re(w, sc, flip), IN::im(w, sc, flip)); },
+                     A.om, cap.halves, blockIdx.x);
+  }
 }
 __global__ __launch_bounds__(256) void k_rxb_detect_peaks(rxb_args A) {
   const rxb_cap &cap = A.caps[blockIdx.y];
@@ -110,7 +166,9 @@ __global__ __launch_bounds__(64) void k_rxb_iv(rxb_args A, unsigned n_caps) {
 // ---- estimator pre-pass ------------------------------------------------------------------------------------------------------------
 // T[b] = Σ_{i in block b} k·p^(end−1−i)·(x[i]−128): what S is right behind block b if it was 0 in front of it.  One workgroup of 256 per
 // block, 16 consecutive samples per thread (Horner), the threads' partial sums weighted by p^(16·(255−t)) and added up.
+template <int K>
 __global__ __launch_bounds__(256) void k_rxb_notch_pre(rxb_args A) {
+  typedef rxb_in<K> IN;
   const rxb_cap &cap = A.caps[blockIdx.y];
   const unsigned PB = A.pre_block, per = PB / 256u;
   const unsigned long long pos = (unsigned long long)blockIdx.x * PB;
@@ -119,7 +177,8 @@ __global__ __launch_bounds__(256) void k_rxb_notch_pre(rxb_args A) {
   __shared__ float2 red[4];
   float2 acc = make_float2(0.f, 0.f);
   if (v.k != 0.f) {
-    const unsigned char *src = cap.in + 2 * (pos + (unsigned long long)threadIdx.x * per);
+    const unsigned char *src = cap.in + IN::kBytes * (pos + (unsigned long long)threadIdx.x * per);
+    if constexpr (K == kRxbU8) {
     for (unsigned i = 0; i < per; i += 8) {
       const uint4 w = *reinterpret_cast<const uint4 *>(src + 2 * i);   // 8 samples (a capture buffer is 16-byte aligned, blocks are multiples of 1024 samples)
       const unsigned ws[4] = {w.x, w.y, w.z, w.w};
@@ -129,6 +188,26 @@ __global__ __launch_bounds__(256) void k_rxb_notch_pre(rxb_args A) {
         for (int h = 0; h < 2; ++h) {
           const unsigned s = ws[q] >> (16 * h);
           const float xr = (float)((int)(s & 255u) - 128), xi = (float)((int)((s >> 8) & 255u) - 128);
+          const float nr = __builtin_fmaf(v.pr, acc.x, __builtin_fmaf(-v.pi, acc.y, v.k * xr));
+          const float ni = __builtin_fmaf(v.pr, acc.y, __builtin_fmaf(v.pi, acc.x, v.k * xi));
+          acc.x = nr; acc.y = ni;
+        }
+      }
+    }
+    } else {
+      // the converted formats: 16 bytes per load as well (8, 4 or 2 samples), the items picked out of the four dwords
+      constexpr unsigned kPer = 16u / (unsigned)IN::kBytes;
+      const float sc = A.in_scale; const unsigned flip = A.in_flip;
+      for (unsigned i = 0; i < per; i += kPer) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(src + IN::kBytes * i);
+        const unsigned ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (unsigned q = 0; q < kPer; ++q) {
+          typename IN::item it;
+          if constexpr (K == kRxbS8) it = ws[q >> 1] >> (16 * (q & 1u));
+          else if constexpr (K == kRxb16) it = ws[q];
+          else it = make_float2(__uint_as_float(ws[2 * q]), __uint_as_float(ws[2 * q + 1]));
+          const float xr = IN::re(it, sc, flip), xi = IN::im(it, sc, flip);
           const float nr = __builtin_fmaf(v.pr, acc.x, __builtin_fmaf(-v.pi, acc.y, v.k * xr));
           const float ni = __builtin_fmaf(v.pr, acc.y, __builtin_fmaf(v.pi, acc.x, v.k * xi));
           acc.x = nr; acc.y = ni;
@@ -176,10 +255,6 @@ __host__ __device__ __forceinline__ float rxb_phase_error(int Ii, int Qi) {
   return __builtin_truncf(pe);                            // the table's (s32) cast
 }
 
-__device__ __forceinline__ float rxb_u8f(unsigned w, int byte) {       // (float)((int)u8 − 128): flip the top bit, sign-extend
-  return (float)(int)(signed char)((w ^ 0x8080u) >> (8 * byte));
-}
-
 // ---- the notch's state for a lane that starts at sample `ws` (a multiple of pre_block) of its capture ----------------------------------
 struct rxb_notch { float pr, pi, k, sr, si; unsigned ivm; };
 __device__ __forceinline__ rxb_notch rxb_notch_start(const rxb_args &A, const rxb_cap &cap, unsigned long long ws) {
@@ -215,6 +290,7 @@ __device__ __forceinline__ void rxb_notch_step(float pr, float pi, float k, floa
 }
 // Test kernel (lsdr_capture_batch_notched): the notched stream the tiles see, written out — one LANE per pre_block samples, the same
 // start state, interval switches and recurrence as rxb_tile.
+template <int K>
 __global__ __launch_bounds__(64) void k_rxb_notch_dump(rxb_args A, unsigned cap_index, unsigned long long n_samples, float2 *out) {
   const rxb_cap &cap = A.caps[cap_index];
   const unsigned long long seg = (unsigned long long)blockIdx.x * 64u + threadIdx.x, ws = seg * A.pre_block;
@@ -222,8 +298,8 @@ __global__ __launch_bounds__(64) void k_rxb_notch_dump(rxb_args A, unsigned cap_
   rxb_notch N = rxb_notch_start(A, cap, ws);
   for (unsigned long long i = ws; i < ws + A.pre_block && i < n_samples; ++i) {
     if ((i & 4095ull) == 0) rxb_notch_block(A, cap, i, N);
-    const unsigned w = reinterpret_cast<const unsigned short *>(cap.in)[i];
-    const float xr = rxb_u8f(w, 0), xi = rxb_u8f(w, 1);
+    const typename rxb_in<K>::item w = rxb_in<K>::ld(cap.in + (unsigned long long)rxb_in<K>::kBytes * i);
+    const float xr = rxb_in<K>::re(w, A.in_scale, A.in_flip), xi = rxb_in<K>::im(w, A.in_scale, A.in_flip);
     float tr, ti;
     rxb_notch_step(N.pr, N.pi, N.k, N.sr, N.si, xr, xi, tr, ti);
     N.sr = tr; N.si = ti;
@@ -246,14 +322,27 @@ __device__ __forceinline__ unsigned rxb_soft_word(int Ii, int Qi, unsigned sym) 
 // LDS staging of the lean tiles: 32 samples per stage + 16 of look-ahead (the next symbol's pair is read up to 3 samples ahead, a timing
 // excursion walks up to omega + 2 ≤ 10): 112-byte rows, 7 KiB per wavefront — 22 wavefronts per CU where the 64-sample stages of
 // rx_tile_tol (11 KiB) allow 14; this kernel lives on wavefronts per SIMD (VALU issue, a dependent chain per symbol).
-struct rxb_stage {
-  static constexpr int kStage = 32, kMargin = 16, kRowBytes = 2 * (kStage + kMargin) + 16;
+// The wider items keep that row: 8-sample stages of 4-byte items are the same 112 bytes (cu16 / cs16: 7 KiB per wavefront, the cu8
+// occupancy), of 8-byte items 208 bytes (cf32: 13 KiB per wavefront, 12 wavefronts per CU) — the look-ahead margin is what a row is made
+// of, and it does not shrink with the stage.
+template <int K> struct rxb_stage {
+  static constexpr int kStage = rxb_in<K>::kStage, kMargin = 16, kRowBytes = rxb_in<K>::kBytes * (kStage + kMargin) + 16;
+  static_assert(kRowBytes % 16 == 0 && kChunk % kStage == 0, "stage geometry");
 };
-static_assert(rxb_stage::kRowBytes % 16 == 0 && kChunk % rxb_stage::kStage == 0, "stage geometry");
+static_assert(rxb_stage<kRxbU8>::kRowBytes == 112 && rxb_stage<kRxbS8>::kRowBytes == 112 && rxb_stage<kRxb16>::kRowBytes == 112 &&
+              rxb_stage<kRxbF32>::kRowBytes == 208, "stage geometry");
 
-template <bool NOTCH, bool SOFT>
+template <bool NOTCH, bool SOFT, int K>
 __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, unsigned j0, int lane, char *lds) {
-  typedef rxb_stage ST;
+  typedef rxb_stage<K> ST;
+  typedef rxb_in<K> IN;
+  typedef typename IN::item item_t;
+  constexpr int kB = IN::kBytes;                                           // bytes per item
+  const float isc = A.in_scale; const unsigned iflip = A.in_flip;          // (kRxbU8 reads neither)
+  // (kRxbU8 calls rxb_u8f where it always did: through rxb_in the compiler flips the sign bit per byte, behind the sign extension — four
+  // more instructions per symbol)
+#define RXB_RE(w) (K == kRxbU8 ? rxb_u8f(rxb_word(w), 0) : IN::re(w, isc, iflip))
+#define RXB_IM(w) (K == kRxbU8 ? rxb_u8f(rxb_word(w), 1) : IN::im(w, isc, iflip))
   constexpr int kStage = ST::kStage, kRowBytes = ST::kRowBytes, kStageLoads = ST::kRowBytes / 16;
   const bool valid = j0 + (unsigned)lane < cap.n_tiles;
   const unsigned j = valid ? j0 + (unsigned)lane : j0;
@@ -268,14 +357,14 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
   const unsigned long long addr = (unsigned long long)cap.in;
   const int delta = (int)(addr & 15ull);
   const unsigned long long cb0 = (unsigned long long)(j0 - 1) * Lc;         // first tile of the wavefront
-  const unsigned long long bytes = ((cap.total_chunks * kChunk + 1ull) * 2ull + (unsigned)delta + 15ull) & ~15ull;
+  const unsigned long long bytes = ((cap.total_chunks * kChunk + 1ull) * (unsigned long long)kB + (unsigned)delta + 15ull) & ~15ull;
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(cap.in) - delta, 0,
                                                                          (int)(bytes > 0xffffffffull ? 0xffffffffu : (unsigned)bytes), 0x00020000);
   unsigned src_off[kStageLoads];
 #pragma unroll
   for (int q = 0; q < kStageLoads; ++q) {
     const unsigned f = (unsigned)q * 1024u + (unsigned)lane * 16u, r = f / (unsigned)kRowBytes, col = f - r * (unsigned)kRowBytes;
-    const unsigned long long tile_byte = (cb0 + (unsigned long long)r * Lc) * (kChunk * 2ull);
+    const unsigned long long tile_byte = (cb0 + (unsigned long long)r * Lc) * (unsigned long long)(kChunk * kB);
     src_off[q] = (j0 + r < cap.n_tiles && tile_byte + col < 0xfff00000ull) ? (unsigned)(tile_byte + col) : 0xfffffff0u;
   }
   const char *const row = lds + lane * kRowBytes + delta;                   // sample s0 of the stage in flight sits here
@@ -333,7 +422,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
   };
   float mu_begin = 0.f, phase_begin = 0.f;
   int n = 0;                                     // sample of the next symbol (tile-relative)
-  unsigned x0w = 0, x1w = 0;                     // the cu8 items of samples n and n + 1
+  item_t x0w = item_t(), x1w = item_t();         // the items of samples n and n + 1
   bool fetched = false;
 
   for (int ci = 0; ci < wave_chunks; ++ci) {
@@ -369,7 +458,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
     for (int sb = 0; sb < kChunk / kStage; ++sb) {
       const int s0 = ci * kChunk + sb * kStage, send = s0 + kStage;
       {
-        const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(s0 * 2);
+        const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(s0 * kB);
 #pragma unroll
         for (int q = 0; q < kStageLoads; ++q)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (rx_lds_ptr)(size_t)(unsigned)(unsigned long long)(lds + q * 1024), 16, src_off[q], soff, 0, 0);
@@ -378,16 +467,16 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
 #endif
         asm volatile("" ::: "memory");
       }
-      const char *ap = row + 2 * (n - s0);       // sample n in this lane's row
+      const char *ap = row + kB * (n - s0);      // sample n in this lane's row
       if (active && !fetched) {
-        x0w = *reinterpret_cast<const unsigned short *>(ap); x1w = *reinterpret_cast<const unsigned short *>(ap + 2);
+        x0w = IN::ld(ap); x1w = IN::ld(ap + kB);
         fetched = true;
       }
       auto symbol = [&](auto body_tag) {
         constexpr bool BODY = decltype(body_tag)::value;
-        const float x0r = rxb_u8f(x0w, 0), x0i = rxb_u8f(x0w, 1), x1r = rxb_u8f(x1w, 0), x1i = rxb_u8f(x1w, 1);
+        const float x0r = RXB_RE(x0w), x0i = RXB_IM(x0w), x1r = RXB_RE(x1w), x1i = RXB_IM(x1w);
         // the items two and three samples on: the next symbol's pair is (x1, r2) or (r2, r3)
-        const unsigned r2 = *reinterpret_cast<const unsigned short *>(ap + 4), r3 = *reinterpret_cast<const unsigned short *>(ap + 6);
+        const item_t r2 = IN::ld(ap + 2 * kB), r3 = IN::ld(ap + 3 * kB);
         float o0r = x0r, o0i = x0i, o1r = x1r, o1i = x1i, t0r = 0.f, t0i = 0.f, t1r = 0.f, t1i = 0.f;
         if (NOTCH) {
           rxb_notch_step(npr, npi, nkk, sr, si, x0r, x0i, t0r, t0i);
@@ -438,17 +527,17 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
         if (NOTCH) { sr = one ? t0r : t1r; si = one ? t0i : t1i; }
         if (ki > 2) {                             // (omega > 2, or a timing excursion): walk the samples in between
           for (int i = 2; i < ki; ++i) {
-            const unsigned w = *reinterpret_cast<const unsigned short *>(ap + 2 * i);
+            const item_t w = IN::ld(ap + kB * i);
             if (NOTCH) {
-              const float xr = rxb_u8f(w, 0), xi = rxb_u8f(w, 1);
+              const float xr = RXB_RE(w), xi = RXB_IM(w);
               float nr, ni;
               rxb_notch_step(npr, npi, nkk, sr, si, xr, xi, nr, ni);
               sr = nr; si = ni;
             }
           }
-          x0w = *reinterpret_cast<const unsigned short *>(ap + 2 * ki); x1w = *reinterpret_cast<const unsigned short *>(ap + 2 * ki + 2);
+          x0w = IN::ld(ap + kB * ki); x1w = IN::ld(ap + kB * ki + kB);
         }
-        n += ki; ap += 2 * ki;
+        n += ki; ap += kB * ki;
       };
       if (body) { while (active && n < send) symbol(std::true_type()); }
       else { while (active && n < send) symbol(std::false_type()); }
@@ -477,11 +566,13 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
     cap.hinfo[j] = th;
     if (j == cap.n_tiles - 1) { cap.state_end->phase = phase; cap.state_end->freqw = freqw; }
   }
+#undef RXB_RE
+#undef RXB_IM
 }
 
-template <bool NOTCH, bool SOFT>
+template <bool NOTCH, bool SOFT, int K>
 __device__ __forceinline__ void rxb_tiles_body(const rxb_args &A) {
-  __shared__ __attribute__((aligned(16))) char lds[64 * rxb_stage::kRowBytes];
+  __shared__ __attribute__((aligned(16))) char lds[64 * rxb_stage<K>::kRowBytes];
   const rxb_cap &cap = A.caps[blockIdx.y];
   if (blockIdx.x == 0) {
     // tile 0: the reference's arithmetic from the constructed state over the first warm_chunks chunks (in front of the first detect
@@ -493,19 +584,25 @@ __device__ __forceinline__ void rxb_tiles_body(const rxb_args &A) {
       a.info = nullptr; a.hstage = cap.hstage; a.hpitch = cap.hpitch; a.hinfo = cap.hinfo; a.ema = cap.ema_scratch; a.ema_wave = cap.ema_scratch + 1;
       if (SOFT) a.stage = reinterpret_cast<lsdr_softsymbol *>(cap.sstage);
       a.state = A.state0; a.state_next = cap.state_end; a.meas = nullptr; a.meas_base = 0; a.cstln = nullptr; a.C = A.C; a.T = A.T;
-      rx_tile_exact<1, LSDR_IN_CU8, true, SOFT>(a);
+      rx_tile_exact<1, rxb_in<K>::kTile0, true, SOFT>(a, A.in_scale, A.in_flip);
     }
     return;
   }
   const unsigned j0 = 1u + (blockIdx.x - 1u) * 64u;
   if (j0 >= cap.n_tiles) return;
-  rxb_tile<NOTCH, SOFT>(A, cap, j0, (int)threadIdx.x, lds);
+  rxb_tile<NOTCH, SOFT, K>(A, cap, j0, (int)threadIdx.x, lds);
 }
 template <bool NOTCH>
-__global__ __launch_bounds__(64) void k_rxb_tiles(rxb_args A) { rxb_tiles_body<NOTCH, false>(A); }
+__global__ __launch_bounds__(64) void k_rxb_tiles(rxb_args A) { rxb_tiles_body<NOTCH, false, kRxbU8>(A); }
 // the soft tiles: held to the packed tiles' five waves per SIMD (the notch variant's live values come to one register more)
 template <bool NOTCH>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_rxb_tiles_soft(rxb_args A) { rxb_tiles_body<NOTCH, true>(A); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_rxb_tiles_soft(rxb_args A) { rxb_tiles_body<NOTCH, true, kRxbU8>(A); }
+// the converted formats (cu8 objects never run these): packed and soft tiles of kind K
+template <bool NOTCH, bool SOFT, int K>
+__global__ __launch_bounds__(64) void k_rxb_tiles_in(rxb_args A) { rxb_tiles_body<NOTCH, SOFT, K>(A); }
+// … the soft tiles of the 2- and 4-byte items: held to five waves per SIMD like k_rxb_tiles_soft (same 7 KiB of LDS; one register over otherwise)
+template <bool NOTCH, int K>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_rxb_tiles_in_soft5(rxb_args A) { rxb_tiles_body<NOTCH, true, K>(A); }
 
 __global__ __launch_bounds__(kSeamBlock) void k_rxb_seam(rxb_args A, float omega, int R, float quad, const uint8_t *relabel) {
   const rxb_cap &cap = A.caps[blockIdx.y];

@@ -131,6 +131,20 @@ def capture_u8(n_packets=140, sps_num=6, sps_den=5, seed=1, amp=75.0, noise_std=
     return iq, ts
 
 
+def capture_s16(n_packets=140, sps_num=6, sps_den=5, seed=1, amp=75.0, noise_std=7.5, lsb=256.0):
+    """capture_u8's signal (the same packets, modulation and noise draws) as cs16: multiplied by `lsb`, rounded to int16, clipped to
+    [-32768, 32767], no offset — with the same seed the analogue signal of capture_u8, quantised 256 times finer (leandvb --s16; scale it
+    by 1 / lsb to the level capture_u8 has).  Returns (int16 IQ array, interleaved re, im; TS packets)."""
+    ts = ts_packets(n_packets)
+    bb = modulate(ts, sps_num, sps_den)
+    rng = np.random.default_rng(seed)
+    x = bb * amp + (rng.standard_normal(len(bb)) + 1j * rng.standard_normal(len(bb))) * noise_std
+    iq = np.empty(2 * len(x), np.int16)
+    iq[0::2] = np.clip(np.rint(x.real * lsb), -32768, 32767)
+    iq[1::2] = np.clip(np.rint(x.imag * lsb), -32768, 32767)
+    return iq, ts
+
+
 def capture_f32(n_packets=140, sps=4, seed=1, rms=1.0, snr_db=20.0):
     """cf32 capture at an integer number of samples per symbol (Es/N0 as in synth.qpsk_baseband)."""
     ts = ts_packets(n_packets)
