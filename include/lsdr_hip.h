@@ -771,6 +771,26 @@ int lsdr_capture_batch_notched(lsdr_capture_batch *b, int i, lsdr_cf32 *out_dev,
 /* HIP events around the tile kernel of every run while enabled: mean duration since the previous call, then sets the switch */
 int lsdr_capture_batch_tile_time(lsdr_capture_batch *b, int enable, float *avg_ms, unsigned *launches);
 
+/* Signal reports: per capture what `leandvb --fd-info` prints — cstln_receiver writes FREQ, SS and MER once per meas_decimation samples
+ * (sdr.h:857-913: the estimators est_insp / est_sp / est_ep of sdr.h:866-889, freqw behind the drift clamp of sdr.h:895-898; leandvb.cc:428-430,
+ * 465, 502, 600-605; leandvb's period is Fs/Finfo).  They tell a weak capture (MER) from a mistuned one (FREQ, held inside
+ * ± 65536/omega/2048 table units per sample around 0) and from one at the wrong level (SS: the LEVEL CONTRACT below asks for about 75).
+ * Both engines, all sample formats, in the batch's own launches: the tiles fold each body chunk's estimator inputs into an affine map
+ * per tile (a chunk belongs to exactly one tile's body; the error vector is taken at the serial gain the tile estimates, as the soft
+ * records are), one more launch per batch composes the maps of every capture from the constructed estimators, and the records follow the
+ * result records into pinned host memory — nothing is synchronised or read on the host between run_async and wait.  Reports inside tile 0
+ * are the reference's bit for bit; the others hold leansdr_amd/tolerance.py's ss_rtol / mer_atol_db / capture_batch_freq_atol against
+ * the serial receiver.  An object with reports off (the default) runs the kernels and launches it would run without this call.
+ * LSDR_E_ARG: a period in (0, 128) (several reports per chunk), i outside [0, n_captures), a batch in flight, lsdr_capture_reports_get
+ * with reports off.  LSDR_E_UNSUPPORTED: a period of 2^31 samples or more that still fits into max_samples. */
+typedef struct { float freq, ss, mer; uint32_t pad; } lsdr_capture_report;   /* freq_tap in cycles per sample; sqrt(est_insp); dB */
+/* period_samples = cstln_receiver::meas_decimation (leandvb: Fs/Finfo); 0 = off (the default).  Not while a batch is in flight.  Buffers
+ * are sized for max_samples here. */
+int lsdr_capture_reports_set(lsdr_capture_batch *b, uint64_t period_samples);
+/* after wait: capture i's reports of the last batch, oldest first (result.samples / period_samples of them); *n = how many there are (may
+ * exceed cap: cap are written); last (may be NULL) = the estimators behind the capture's last chunk */
+int lsdr_capture_reports_get(lsdr_capture_batch *b, int i, lsdr_capture_report *out, size_t cap, size_t *n, lsdr_capture_report *last);
+
 /* Other sample formats: the same object for captures that are not cu8.  leandvb reads five formats into the same graph (leandvb.cc:208-261);
  * here the format replaces the graph's first block(s), fused into every load that touches a capture — the converted, scaled stream never
  * exists in device memory:

@@ -340,6 +340,14 @@ _sig("lsdr_capture_batch_notched", C.c_int, [vp, C.c_int, vp, c_sz])
 _sig("lsdr_capture_batch_tile_time", C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint)])
 
 
+class CaptureReport(C.Structure):
+    _fields_ = [("freq", C.c_float), ("ss", C.c_float), ("mer", C.c_float), ("pad", C.c_uint32)]
+
+
+_sig("lsdr_capture_reports_set", C.c_int, [vp, C.c_uint64])
+_sig("lsdr_capture_reports_get", C.c_int, [vp, C.c_int, C.POINTER(CaptureReport), c_sz, psz, C.POINTER(CaptureReport)])
+
+
 class HsBatchCfg(C.Structure):
     _fields_ = [("n_captures", C.c_int), ("max_samples", C.c_size_t), ("omega", C.c_float), ("freq", C.c_float), ("allow_drift", C.c_int),
                 ("fastlock", C.c_int), ("tile_len", C.c_uint), ("tile_warmup", C.c_uint), ("reserved", C.c_int * 8)]
@@ -853,7 +861,7 @@ class CaptureBatch:
     --f32 --float-scale; the converted samples must have an RMS near 75 (the level contract, include/lsdr_hip.h)."""
 
     def __init__(self, ctx, n_captures, max_samples, omega, fec=FEC12, anf=1, tile_len=0, tile_warmup=0, notch_k=0.0, notch_decimation=0,
-                 unlocked_window=0, aux_cus=0, viterbi=None, in_format=IN_CU8, in_scale=0.0):
+                 unlocked_window=0, aux_cus=0, viterbi=None, in_format=IN_CU8, in_scale=0.0, reports=0):
         self.ctx, self.n = ctx, int(n_captures)
         cfg = CaptureBatchCfg()
         cfg.n_captures, cfg.max_samples, cfg.omega, cfg.fec, cfg.anf = self.n, int(max_samples), omega, fec, anf
@@ -878,6 +886,12 @@ class CaptureBatch:
             check(lib.lsdr_capture_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
         self.h = h
         self._res = (CaptureResult * self.n)()
+        if reports:
+            try:
+                self.set_reports(reports)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if self.h:
@@ -966,6 +980,20 @@ class CaptureBatch:
         out = self.ctx.download(d, np.complex64, int(n))
         d.free()
         return out
+
+    def set_reports(self, period_samples):
+        """Signal reports once per period_samples (cstln_receiver::meas_decimation; 0: off).  Not while a batch is in flight."""
+        check(lib.lsdr_capture_reports_set(self.h, int(period_samples)))
+
+    def reports(self, i):
+        """Capture i's reports of the last batch, oldest first: dict(freq, ss, mer: float32 arrays; last: the same three behind the
+        capture's last chunk, as a float32 array [freq, ss, mer])."""
+        n, last = c_sz(), CaptureReport()
+        check(lib.lsdr_capture_reports_get(self.h, int(i), None, 0, C.byref(n), C.byref(last)))
+        buf = (CaptureReport * max(1, n.value))()
+        check(lib.lsdr_capture_reports_get(self.h, int(i), buf, n.value, C.byref(n), C.byref(last)))
+        a = np.frombuffer(buf, np.float32).reshape(-1, 4)[:n.value]
+        return dict(freq=a[:, 0].copy(), ss=a[:, 1].copy(), mer=a[:, 2].copy(), last=np.array([last.freq, last.ss, last.mer], np.float32))
 
     def tile_time(self, enable):
         ms, n = C.c_float(), C.c_uint()

@@ -12,6 +12,9 @@
 //
 // Other sample formats (lsdr_capture_any_create): `leandvb --s8 / --u16 / --s16 / --f32 --float-scale S` (leandvb.cc:208-261) in place of
 // `--u8`.  Format and scale only select the front end's kernels (rxb_device.h converts in its loads); everything here is format-blind.
+//
+// Signal reports (lsdr_capture_reports_set / _get): leandvb's --fd-info per capture — FREQ, SS, MER once per meas_decimation samples
+// (sdr.h:857-913).  The front end records and scans the estimators in its own launches (rxb_device.h); here only the libm scalars.
 #include "lsdr_internal.h"
 
 struct lsdr_capture_batch {
@@ -285,6 +288,37 @@ int lsdr_capture_batch_notched(lsdr_capture_batch *b, int i, lsdr_cf32 *out_dev,
   LSDR_ARG(b && i >= 0 && i < b->cfg.n_captures);
   if (b->in_flight) { lsdr_set_error("capture_batch: a batch is in flight (lsdr_capture_batch_wait first)"); return LSDR_E_ARG; }
   return lsdr_rxb_notched(b->rx, (unsigned)i, out_dev, n);
+}
+// Signal reports: what leandvb's --fd-info prints per capture (cstln_receiver's FREQ / SS / MER pipes, sdr.h:857-913, leandvb.cc:428-430,
+// 465, 502, 600-605).  The estimators come from the front end's launches (rxb_device.h: REP tiles, k_rxb_reports); the libm scalars of
+// sdr.h:907-911 are taken here, as rx_run_tiled takes them.
+static lsdr_capture_report capture_report(const lsdr_rxb_report &m) {
+  lsdr_capture_report r;
+  r.freq = m.freqw / 65536;
+  r.ss = sqrtf(m.est_insp);
+  r.mer = m.est_ep ? 10 * logf(m.est_sp / m.est_ep) / logf(10) : 0;
+  r.pad = 0;
+  return r;
+}
+int lsdr_capture_reports_set(lsdr_capture_batch *b, uint64_t period_samples) {
+  LSDR_ARG(b);
+  if (b->in_flight) { lsdr_set_error("capture_batch: a batch is in flight (lsdr_capture_batch_wait first)"); return LSDR_E_ARG; }
+  if (b->ctx_aux) LSDR_HIP(hipStreamSynchronize(b->ctx_aux->stream));
+  return lsdr_rxb_set_reports(b->rx, period_samples);
+}
+int lsdr_capture_reports_get(lsdr_capture_batch *b, int i, lsdr_capture_report *out, size_t cap, size_t *n, lsdr_capture_report *last) {
+  LSDR_ARG(b && n && i >= 0 && i < b->cfg.n_captures && (out || !cap));
+  if (b->in_flight) { lsdr_set_error("capture_batch: a batch is in flight (lsdr_capture_batch_wait first)"); return LSDR_E_ARG; }
+  if (!lsdr_rxb_reports_on(b->rx)) { lsdr_set_error("capture_batch: reports are off (lsdr_capture_reports_set)"); return LSDR_E_ARG; }
+  const lsdr_rxb_report *slots = nullptr;
+  lsdr_rxb_report fin;
+  size_t have = 0;
+  LSDR_TRY(lsdr_rxb_reports(b->rx, (unsigned)i, &slots, &have, &fin));
+  if (!b->waited) have = 0;                                                // (no batch yet)
+  for (size_t q = 0; q < have && q < cap; ++q) out[q] = capture_report(slots[q]);
+  *n = have;
+  if (last) *last = capture_report(fin);
+  return LSDR_OK;
 }
 int lsdr_capture_batch_tile_time(lsdr_capture_batch *b, int enable, float *avg_ms, unsigned *launches) {
   LSDR_ARG(b);

@@ -110,6 +110,11 @@ int lsdr_rxb_bins(lsdr_rxb *b, unsigned i, int *bins, unsigned cap, unsigned *n)
 int lsdr_rxb_seam_stats(lsdr_rxb *b, unsigned i, unsigned long long *total, unsigned *dup, unsigned *miss, unsigned *bad);
 int lsdr_rxb_tile_time(lsdr_rxb *b, int enable, float *avg_ms, unsigned *launches);
 int lsdr_rxb_notched(lsdr_rxb *b, unsigned i, lsdr_cf32 *out_dev, size_t n);
+// signal reports: the estimators at a measurement instant (cstln_receiver.hip's rx_meas); `a` and `tile` are the scan's own
+struct lsdr_rxb_report { float freqw, est_insp, est_sp, est_ep, a; unsigned tile; };
+int lsdr_rxb_set_reports(lsdr_rxb *b, unsigned long long period_samples);
+int lsdr_rxb_reports_on(const lsdr_rxb *b);
+int lsdr_rxb_reports(const lsdr_rxb *b, unsigned i, const lsdr_rxb_report **slots, size_t *n, lsdr_rxb_report *last);
 // fec.hip (tail_host.h): the FEC tail of every capture, counts on the device
 struct lsdr_tail;
 struct lsdr_tail_result {          // = tail_device.h's tail_result

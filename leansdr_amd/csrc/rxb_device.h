@@ -16,6 +16,10 @@
 //   k_rxb_tiles_soft<NOTCH> / k_rxb_compact_soft   the same tiles with SOFT symbols out (leandvb --viterbi: viterbi_sync reads
 //                        softsymbol{cost, symbol}, sdr.h:287-290): one 4-byte record per body symbol, staged transposed (row = symbol
 //                        index, column = tile) and compacted through LDS into one contiguous lsdr_softsymbol array per capture
+//   k_rxb_tiles_rep<NOTCH, SOFT, K> / k_rxb_reports   signal reports (lsdr_capture_reports_set: cstln_receiver's FREQ / SS / MER pipes,
+//                        sdr.h:857-913): the same tiles with the estimators' affine map per tile and a slot per measurement instant, and the
+//                        scan that composes a capture's maps from the constructed estimators (rxb_rep below).  Only objects that asked for
+//                        reports launch them.
 //
 // The notch inside a tile.  sdr.h:119-138 with one slot is, per detect interval, estim[n] = (1−k)·estim[n−1] + k·x[n]·conj(e[n]),
 // out[n] = x[n] − estim[n]·e[n], e[n] = exp(j2π·bin·n/4096) (n counted from the block start; 4096·bin/4096 is whole, so the phasor runs
@@ -59,6 +63,15 @@ struct rxb_cap {
   unsigned long long *count_out;       // → the capture's entry of a contiguous uint64[n_captures]: symbols in out_soft
 };
 
+// Signal reports of one capture (`--fd-info`: cstln_receiver writes FREQ / SS / MER once per meas_decimation samples, sdr.h:857-913).
+// The estimators behind them are EMAs with a constant pole (rx_ema_map, cstln_receiver.hip): a tile records the affine map of its body
+// chunks, and for the chunk that holds a measurement instant a slot with the partial map up to there; k_rxb_reports composes the maps
+// from the constructed estimators and turns the slots into values.
+struct rxb_rep {
+  rx_ema_map *map;                     // [n_tiles] the tile's map; behind k_rxb_reports the estimator VALUES in front of the tile (bi, bs, be)
+  rx_meas *slot;                       // [reports + 1] one per measurement instant, oldest first; then the values behind the last chunk
+};
+
 struct rxb_args {
   const rxb_cap *caps;
   const unsigned *iv_of_block;         // [blocks of 4096 samples] detect interval a block belongs to (the same for every capture)
@@ -72,7 +85,11 @@ struct rxb_args {
   rx_tables T;
   float in_scale;                      // the converted formats (rxb_in below): scaler's factor (1: none), the 16-bit items' bias as an xor mask
   unsigned in_flip;
+  // signal reports (lsdr_capture_reports_set; read by the REP tiles and k_rxb_reports only)
+  const rxb_rep *rep;                  // [captures]
+  unsigned rep_period;                 // cstln_receiver::meas_decimation in samples (0: no instant inside a capture, the final record only)
 };
+
 
 // ---- sample formats ----------------------------------------------------------------------------------------------------------------
 // Every kernel that reads a capture converts in its loads: value = float(item − Z)·in_scale (cconverter<T,Z,f32,0,1,1>, dsp.h:40-50, exact;
@@ -325,6 +342,7 @@ __device__ __forceinline__ unsigned rxb_soft_word(int Ii, int Qi, unsigned sym) 
 // The wider items keep that row: 8-sample stages of 4-byte items are the same 112 bytes (cu16 / cs16: 7 KiB per wavefront, the cu8
 // occupancy), of 8-byte items 208 bytes (cf32: 13 KiB per wavefront, 12 wavefronts per CU) — the look-ahead margin is what a row is made
 // of, and it does not shrink with the stage.
+constexpr float kSigPowerQpsk = 5618.0f;        // 53² + 53²: sig_power of every QPSK point (sdr.h:873-889)
 template <int K> struct rxb_stage {
   static constexpr int kStage = rxb_in<K>::kStage, kMargin = 16, kRowBytes = rxb_in<K>::kBytes * (kStage + kMargin) + 16;
   static_assert(kRowBytes % 16 == 0 && kChunk % kStage == 0, "stage geometry");
@@ -332,8 +350,13 @@ template <int K> struct rxb_stage {
 static_assert(rxb_stage<kRxbU8>::kRowBytes == 112 && rxb_stage<kRxbS8>::kRowBytes == 112 && rxb_stage<kRxb16>::kRowBytes == 112 &&
               rxb_stage<kRxbF32>::kRowBytes == 208, "stage geometry");
 
-template <bool NOTCH, bool SOFT, int K>
+// REP (signal reports, rxb_rep): per body chunk the estimator inputs of sdr.h:866-889 folded into the tile's map, and a slot where a
+// measurement instant falls into the chunk.  insp does not depend on the gain and sig_power is 53² + 53²; ev_power = |s − c|² of the
+// chunk's last symbol does: it is taken at the serial gain the soft tiles estimate (`pavg` / `crat` below, which the REP tiles of the
+// default engine carry too), not at the tile's own, which starts from the constructed AGC.
+template <bool NOTCH, bool SOFT, int K, bool REP = false>
 __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, unsigned j0, int lane, char *lds) {
+  constexpr bool GAIN = SOFT || REP;                                       // the second power estimator runs
   typedef rxb_stage<K> ST;
   typedef rxb_in<K> IN;
   typedef typename IN::item item_t;
@@ -420,6 +443,14 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
     const int Ic = (int)Is, Qc = (int)Qs;
     return rxb_soft_word(Ic, Qc, (((unsigned)Ic >> 31) << 1) | ((unsigned)Qc >> 31));
   };
+  // REP: the body's map est ↦ ma·est + b (the b of est_sp is 5618·(1 − ma): its input is constant); the measurement counter of
+  // sdr.h:905-913 at the body's first chunk (meas_count = 0 at the capture's first sample) and the slot the next instant fills
+  float ma = 1.f, mbi = 0.f, mbe = 0.f;
+  unsigned mcount = 0, mslot = 0;
+  if (REP && A.rep_period) {
+    const unsigned long long pos = (cb + Wc) * (unsigned long long)kChunk, q = pos / A.rep_period;
+    mslot = (unsigned)q; mcount = (unsigned)(pos - q * A.rep_period);
+  }
   float mu_begin = 0.f, phase_begin = 0.f;
   int n = 0;                                     // sample of the next symbol (tile-relative)
   item_t x0w = item_t(), x1w = item_t();         // the items of samples n and n + 1
@@ -434,7 +465,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
       const float over = (float)(n - ci * kChunk);
       mu_begin = mu + over; phase_begin = phase - over * freqw;
       got = hcnt; hwarm = hacc; hnwarm = hcnt < 16u ? hcnt : 16u; hcnt = 0;
-      if (SOFT && got) {
+      if (GAIN && got) {
         pavg = __builtin_fmaf(__builtin_exp2f((float)(cb + Wc) * __builtin_log2f(k1)), S0->est_insp - pavg, pavg);
         soft_gain(pavg);
       }
@@ -486,7 +517,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
         // linear_sampler::interp (sdr.h:614-623), one derotation
         const float q1r = __builtin_fmaf(o1r, cf, -(o1i * sf)), q1i = __builtin_fmaf(o1r, sf, o1i * cf);
         g0r = __builtin_fmaf(mu, q1r - o0r, o0r); g0i = __builtin_fmaf(mu, q1i - o0i, o0i);
-        if (SOFT && !BODY) pavg = __builtin_fmaf(__builtin_fmaf(g0r, g0r, __builtin_fmaf(g0i, g0i, -pavg)), 1.0f / 128.0f, pavg);
+        if (GAIN && !BODY) pavg = __builtin_fmaf(__builtin_fmaf(g0r, g0r, __builtin_fmaf(g0i, g0i, -pavg)), 1.0f / 128.0f, pavg);
         const float prev = phase * (-1.0f / 65536.0f);
         const float ear = __builtin_amdgcn_cosf(prev) * agc, eai = __builtin_amdgcn_sinf(prev) * agc;
         const float svr = __builtin_fmaf(g0r, ear, -(g0i * eai)), svi = __builtin_fmaf(g0r, eai, g0i * ear);
@@ -548,10 +579,24 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
         const float insp = g0r * g0r + g0i * g0i;
         est_insp = __builtin_fmaf(insp, kk, est_insp * k1);
         if (est_insp) agc = kCstlnAmp / __builtin_sqrtf(est_insp);
-        if (SOFT && body) { pavg = __builtin_fmaf(insp, kk, pavg * k1); soft_gain(pavg); }
+        if (REP && body) {                                                   // sdr.h:873-889: the chunk's last symbol, at the gain it was sampled with
+          const float evr = __builtin_fmaf(h1pr, crat, -h1cr), evi = __builtin_fmaf(h1pi, crat, -h1ci);
+          ma *= k1;
+          mbi = __builtin_fmaf(insp, kk, mbi * k1);
+          mbe = __builtin_fmaf(__builtin_fmaf(evr, evr, evi * evi), kk, mbe * k1);
+        }
+        if (GAIN && body) { pavg = __builtin_fmaf(insp, kk, pavg * k1); soft_gain(pavg); }
       }
       if (!C.allow_drift) {                                                  // sdr.h:895-898
         if (freqw < min_f || freqw > max_f) freqw = (max_f + min_f) / 2;
+      }
+      if (REP && body && A.rep_period) {                                     // sdr.h:905-913 (a period is at least a chunk: one instant at most)
+        mcount += (unsigned)kChunk;
+        if (mcount >= A.rep_period) {
+          mcount -= A.rep_period;
+          rx_meas mm; mm.freqw = freqw; mm.a = ma; mm.est_insp = mbi; mm.est_sp = kSigPowerQpsk * (1.0f - ma); mm.est_ep = mbe; mm.tile = j;
+          A.rep[blockIdx.y].slot[mslot++] = mm;
+        }
       }
     }
   }
@@ -565,12 +610,13 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
     th.count = hcnt; th.has_pre = got ? 1u : 0u; th.n_warm = hnwarm; th.warm_tail = hwarm; th.body_tail = hacc;
     cap.hinfo[j] = th;
     if (j == cap.n_tiles - 1) { cap.state_end->phase = phase; cap.state_end->freqw = freqw; }
+    if (REP) { rx_ema_map m; m.a = ma; m.bi = mbi; m.bs = kSigPowerQpsk * (1.0f - ma); m.be = mbe; A.rep[blockIdx.y].map[j] = m; }
   }
 #undef RXB_RE
 #undef RXB_IM
 }
 
-template <bool NOTCH, bool SOFT, int K>
+template <bool NOTCH, bool SOFT, int K, bool REP = false>
 __device__ __forceinline__ void rxb_tiles_body(const rxb_args &A) {
   __shared__ __attribute__((aligned(16))) char lds[64 * rxb_stage<K>::kRowBytes];
   const rxb_cap &cap = A.caps[blockIdx.y];
@@ -584,13 +630,17 @@ __device__ __forceinline__ void rxb_tiles_body(const rxb_args &A) {
       a.info = nullptr; a.hstage = cap.hstage; a.hpitch = cap.hpitch; a.hinfo = cap.hinfo; a.ema = cap.ema_scratch; a.ema_wave = cap.ema_scratch + 1;
       if (SOFT) a.stage = reinterpret_cast<lsdr_softsymbol *>(cap.sstage);
       a.state = A.state0; a.state_next = cap.state_end; a.meas = nullptr; a.meas_base = 0; a.cstln = nullptr; a.C = A.C; a.T = A.T;
+      if (REP) {                                 // tile 0 owns chunks [0, warm_chunks): its slots and its (constant) map hold exact values
+        a.ema_wave = A.rep[blockIdx.y].map;
+        if (A.rep_period) { a.meas = A.rep[blockIdx.y].slot; a.C.meas_decimation = A.rep_period; }
+      }
       rx_tile_exact<1, rxb_in<K>::kTile0, true, SOFT>(a, A.in_scale, A.in_flip);
     }
     return;
   }
   const unsigned j0 = 1u + (blockIdx.x - 1u) * 64u;
   if (j0 >= cap.n_tiles) return;
-  rxb_tile<NOTCH, SOFT, K>(A, cap, j0, (int)threadIdx.x, lds);
+  rxb_tile<NOTCH, SOFT, K, REP>(A, cap, j0, (int)threadIdx.x, lds);
 }
 template <bool NOTCH>
 __global__ __launch_bounds__(64) void k_rxb_tiles(rxb_args A) { rxb_tiles_body<NOTCH, false, kRxbU8>(A); }
@@ -603,6 +653,63 @@ __global__ __launch_bounds__(64) void k_rxb_tiles_in(rxb_args A) { rxb_tiles_bod
 // … the soft tiles of the 2- and 4-byte items: held to five waves per SIMD like k_rxb_tiles_soft (same 7 KiB of LDS; one register over otherwise)
 template <bool NOTCH, int K>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_rxb_tiles_in_soft5(rxb_args A) { rxb_tiles_body<NOTCH, true, K>(A); }
+
+// the tiles with signal reports (rxb_rep), every kind: objects that have not asked for reports never run these
+template <bool NOTCH, bool SOFT, int K>
+__global__ __launch_bounds__(64) void k_rxb_tiles_rep(rxb_args A) { rxb_tiles_body<NOTCH, SOFT, K, true>(A); }
+
+// Scan of a capture's tile maps, one workgroup per capture (blockIdx.x), behind the tiles: rx_ema_body's scheme.  Thread t composes its
+// run of consecutive tiles, the runs are scanned across the workgroup, and every thread walks its tiles again from the values in front of
+// them — from the constructed estimators for tile 0 — leaving those values in map[] and, behind the last tile, the final record
+// slot[n_rep] (with the freqw the last tile left).  Then every slot's partial map is applied to the values in front of its tile.
+constexpr unsigned kRxbRepThreads = 256;
+__global__ __launch_bounds__(kRxbRepThreads) void k_rxb_reports(rxb_args A) {
+  const rxb_cap &cap = A.caps[blockIdx.x];
+  const rxb_rep R = A.rep[blockIdx.x];
+  const unsigned n_tiles = cap.n_tiles;
+  if (!n_tiles) return;
+  const unsigned n_rep = A.rep_period ? (unsigned)(cap.total_chunks * kChunk / A.rep_period) : 0u;
+  __shared__ rx_ema_map s_wave[kRxbRepThreads / 64];
+  const unsigned t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+  const unsigned per = (n_tiles + kRxbRepThreads - 1) / kRxbRepThreads;
+  const unsigned lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+  rx_ema_map m; m.a = 1.f; m.bi = m.bs = m.be = 0.f;
+  for (unsigned i = lo; i < hi; ++i) m = ema_then(m, R.map[i]);
+  rx_ema_map inc = m;                            // inclusive scan over the lanes of a wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    rx_ema_map o;
+    o.a = __shfl_up(inc.a, d, 64); o.bi = __shfl_up(inc.bi, d, 64); o.bs = __shfl_up(inc.bs, d, 64); o.be = __shfl_up(inc.be, d, 64);
+    if (lane >= (unsigned)d) inc = ema_then(o, inc);
+  }
+  if (lane == 63) s_wave[wv] = inc;
+  __syncthreads();
+  rx_ema_map pre; pre.a = 1.f; pre.bi = pre.bs = pre.be = 0.f;
+  for (unsigned i = 0; i < wv; ++i) pre = ema_then(pre, s_wave[i]);
+  rx_ema_map exl;                                // exclusive: lanes before this one in the wave
+  exl.a = __shfl_up(inc.a, 1, 64); exl.bi = __shfl_up(inc.bi, 1, 64); exl.bs = __shfl_up(inc.bs, 1, 64); exl.be = __shfl_up(inc.be, 1, 64);
+  if (lane == 0) { exl.a = 1.f; exl.bi = exl.bs = exl.be = 0.f; }
+  pre = ema_then(pre, exl);
+  const rx_state_dev *S0 = A.state0;
+  float vi = pre.a * S0->est_insp + pre.bi, vs = pre.a * S0->est_sp + pre.bs, ve = pre.a * S0->est_ep + pre.be;
+  for (unsigned i = lo; i < hi; ++i) {
+    const rx_ema_map mi = R.map[i];
+    rx_ema_map v; v.a = 0.f; v.bi = vi; v.bs = vs; v.be = ve;
+    R.map[i] = v;
+    vi = mi.a * vi + mi.bi; vs = mi.a * vs + mi.bs; ve = mi.a * ve + mi.be;
+  }
+  if (lo < hi && hi == n_tiles) {
+    rx_meas mm; mm.freqw = cap.state_end->freqw; mm.a = 0.f; mm.est_insp = vi; mm.est_sp = vs; mm.est_ep = ve; mm.tile = n_tiles - 1;
+    R.slot[n_rep] = mm;
+  }
+  __syncthreads();
+  for (unsigned q = t; q < n_rep; q += kRxbRepThreads) {
+    rx_meas mm = R.slot[q];
+    const rx_ema_map v = R.map[mm.tile < n_tiles ? mm.tile : 0u];
+    mm.est_insp = mm.a * v.bi + mm.est_insp; mm.est_sp = mm.a * v.bs + mm.est_sp; mm.est_ep = mm.a * v.be + mm.est_ep;
+    R.slot[q] = mm;
+  }
+}
 
 __global__ __launch_bounds__(kSeamBlock) void k_rxb_seam(rxb_args A, float omega, int R, float quad, const uint8_t *relabel) {
   const rxb_cap &cap = A.caps[blockIdx.y];

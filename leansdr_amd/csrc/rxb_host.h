@@ -33,6 +33,15 @@ struct lsdr_rxb {
   int kind;                        // the kernels' kind (rxb_device.h: kRxbU8 …) and what goes with it
   unsigned item_bytes, in_flip;
   float in_scale;                  // 1: none
+  // signal reports (lsdr_rxb_set_reports; off: rep_on false, nothing allocated, the kernels and launches of an object without them)
+  bool rep_on;
+  unsigned long long rep_period;   // as given
+  unsigned rep_period_k;           // what the kernels count with (0: the period is longer than any capture of this object)
+  size_t rep_pitch;                // slots per capture, the final record included
+  rxb_rep *d_rep; rx_meas *d_slots, *h_slots;   // [n] records, [n·rep_pitch] slots, their pinned copy (filled behind every launch)
+  std::vector<void *> rep_owned;   // the captures' map arrays
+  size_t rep_n;                    // reports per capture of the last launch
+  bool rep_none;                   // … which ran no chunk: the constructed estimators are the final record
 };
 
 static int rxb_alloc(lsdr_rxb *b, void **p, size_t bytes) {
@@ -189,9 +198,67 @@ int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft,
   return LSDR_OK;
 }
 
+static void rxb_reports_free(lsdr_rxb *b) {
+  for (void *p : b->rep_owned) (void)hipFree(p);
+  b->rep_owned.clear();
+  if (b->d_rep) (void)hipFree(b->d_rep);
+  if (b->d_slots) (void)hipFree(b->d_slots);
+  if (b->h_slots) (void)hipHostFree(b->h_slots);
+  b->d_rep = nullptr; b->d_slots = nullptr; b->h_slots = nullptr;
+  b->rep_on = false; b->rep_period = 0; b->rep_period_k = 0; b->rep_pitch = 0; b->rep_n = 0; b->rep_none = true;
+}
+
+// period_samples = cstln_receiver::meas_decimation; 0: off.  The previous launch of this object must have completed.  Buffers for max_samples.
+int lsdr_rxb_set_reports(lsdr_rxb *b, unsigned long long period_samples) {
+  LSDR_ARG(b);
+  if (period_samples && period_samples < (unsigned long long)kChunk) {
+    lsdr_set_error("capture_batch: a report period below %d samples (got %llu) is several reports per chunk", kChunk, period_samples); return LSDR_E_ARG;
+  }
+  LSDR_HIP(hipSetDevice(b->ctx->device));
+  LSDR_HIP(hipStreamSynchronize(b->ctx->stream));
+  rxb_reports_free(b);
+  if (!period_samples) return LSDR_OK;
+  const size_t reports = (size_t)((unsigned long long)b->max_samples / period_samples);
+  if (reports && period_samples >= (1ull << 31)) {                              // (the tiles count samples up to the next instant in 32 bits)
+    lsdr_set_error("capture_batch: a report period of %llu samples is beyond the tiles' 32-bit counter", period_samples); return LSDR_E_UNSUPPORTED;
+  }
+  b->rep_period = period_samples; b->rep_period_k = reports ? (unsigned)period_samples : 0u;
+  b->rep_pitch = reports + 1;
+  std::vector<rxb_rep> recs(b->n);
+  LSDR_HIP(hipMalloc((void **)&b->d_slots, b->n * b->rep_pitch * sizeof(rx_meas)));
+  LSDR_HIP(hipMemset(b->d_slots, 0, b->n * b->rep_pitch * sizeof(rx_meas)));
+  LSDR_HIP(hipHostMalloc((void **)&b->h_slots, b->n * b->rep_pitch * sizeof(rx_meas), hipHostMallocDefault));
+  memset(b->h_slots, 0, b->n * b->rep_pitch * sizeof(rx_meas));
+  for (unsigned i = 0; i < b->n; ++i) {
+    void *p = nullptr;
+    LSDR_HIP(hipMalloc(&p, (size_t)b->max_tiles * sizeof(rx_ema_map)));
+    b->rep_owned.push_back(p);
+    recs[i].map = static_cast<rx_ema_map *>(p); recs[i].slot = b->d_slots + (size_t)i * b->rep_pitch;
+  }
+  LSDR_HIP(hipMalloc((void **)&b->d_rep, b->n * sizeof(rxb_rep)));
+  LSDR_HIP(hipMemcpy(b->d_rep, recs.data(), b->n * sizeof(rxb_rep), hipMemcpyHostToDevice));
+  b->rep_on = true;
+  return LSDR_OK;
+}
+int lsdr_rxb_reports_on(const lsdr_rxb *b) { return b && b->rep_on ? 1 : 0; }
+// capture i's estimator records of the last launch (valid once the stream has passed it): *n of them at *slots, then the final record
+int lsdr_rxb_reports(const lsdr_rxb *b, unsigned i, const lsdr_rxb_report **slots, size_t *n, lsdr_rxb_report *last) {
+  LSDR_ARG(b && i < b->n && slots && n && last && b->rep_on);
+  static_assert(sizeof(lsdr_rxb_report) == sizeof(rx_meas) && offsetof(lsdr_rxb_report, est_ep) == offsetof(rx_meas, est_ep), "lsdr_rxb_report mirrors rx_meas");
+  const rx_meas *s = b->h_slots + (size_t)i * b->rep_pitch;
+  *slots = reinterpret_cast<const lsdr_rxb_report *>(s); *n = b->rep_none ? 0 : b->rep_n;
+  if (b->rep_none) {
+    const rx_state_dev &st = b->proto->st_initial;
+    last->freqw = st.freqw; last->est_insp = st.est_insp; last->est_sp = st.est_sp; last->est_ep = st.est_ep; last->a = 0.f; last->tile = 0;
+  } else
+    memcpy(last, s + b->rep_n, sizeof(*last));
+  return LSDR_OK;
+}
+
 void lsdr_rxb_destroy(lsdr_rxb *b) {
   if (!b) return;
   (void)hipStreamSynchronize(b->ctx->stream);
+  rxb_reports_free(b);
   for (void *p : b->owned) (void)hipFree(p);
   (void)hipFree(b->d_caps); if (b->h_caps) (void)hipHostFree(b->h_caps);
   (void)hipFree(b->d_res); if (b->h_res) (void)hipHostFree(b->h_res); (void)hipFree(b->d_state_end); (void)hipFree(b->d_state0); (void)hipFree(b->d_ema); (void)hipFree(b->d_counts);
@@ -210,6 +277,7 @@ static void rxb_fill_args(const lsdr_rxb *b, rxb_args &A) {
   A.nk = b->nk; A.l2omk = (float)log2((double)(1.0f - b->nk));
   rx_fill_consts(b->proto, A.C, A.T);
   A.in_scale = b->in_scale; A.in_flip = b->in_flip;
+  A.rep = b->d_rep; A.rep_period = b->rep_period_k;
 }
 
 // the kernels of the object's kind (cu8: its own instantiations, the ones it had before there were other formats)
@@ -221,6 +289,19 @@ template <int K> static rxb_kernel_t rxb_tiles_of(bool notch, bool soft) {
     else return notch ? k_rxb_tiles_in_soft5<true, K> : k_rxb_tiles_in_soft5<false, K>;
   }
   return notch ? k_rxb_tiles_in<true, false, K> : k_rxb_tiles_in<false, false, K>;
+}
+// … with signal reports
+template <int K> static rxb_kernel_t rxb_tiles_rep_of(bool notch, bool soft) {
+  if (soft) return notch ? k_rxb_tiles_rep<true, true, K> : k_rxb_tiles_rep<false, true, K>;
+  return notch ? k_rxb_tiles_rep<true, false, K> : k_rxb_tiles_rep<false, false, K>;
+}
+static rxb_kernel_t rxb_kernel_tiles_rep(int kind, bool notch, bool soft) {
+  switch (kind) {
+    case kRxbS8: return rxb_tiles_rep_of<kRxbS8>(notch, soft);
+    case kRxb16: return rxb_tiles_rep_of<kRxb16>(notch, soft);
+    case kRxbF32: return rxb_tiles_rep_of<kRxbF32>(notch, soft);
+  }
+  return rxb_tiles_rep_of<kRxbU8>(notch, soft);
 }
 static rxb_kernel_t rxb_kernel_tiles(int kind, bool notch, bool soft) {
   switch (kind) {
@@ -256,6 +337,7 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
   const rxb_geom g = rxb_geometry(b, n_samples);
   *consumed = (size_t)g.chunks * kChunk;
   b->n_det = g.n_det; b->n_pre = g.n_pre; b->n_tiles = g.n_tiles; b->total_chunks = g.chunks;
+  b->rep_n = b->rep_period ? (size_t)(g.chunks * kChunk / b->rep_period) : 0; b->rep_none = !g.chunks;
   if (b->anf && b->geom_samples != n_samples) {                               // detect points of this capture length (the same for every capture)
     std::vector<unsigned> ivb(g.n_blocks ? g.n_blocks : 1, 0u), det(g.n_det + 1, 0u);
     long long phase = 0;
@@ -301,7 +383,7 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
   const unsigned blocks = 1 + (g.n_tiles - 1 + 63) / 64;
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_pre, sa)); LSDR_HIP(hipStreamWaitEvent(st, b->ev_pre, 0)); }
   if (b->timing) { LSDR_HIP(hipEventRecord(b->tev0, st)); }
-  hipLaunchKernelGGL(rxb_kernel_tiles(b->kind, notch, b->soft), dim3(blocks, b->n), dim3(64), 0, st, A);
+  hipLaunchKernelGGL(b->rep_on ? rxb_kernel_tiles_rep(b->kind, notch, b->soft) : rxb_kernel_tiles(b->kind, notch, b->soft), dim3(blocks, b->n), dim3(64), 0, st, A);
   if (b->timing) { LSDR_HIP(hipEventRecord(b->tev1, st)); b->tev_pending = true; }
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_tiles, st)); LSDR_HIP(hipStreamWaitEvent(sa, b->ev_tiles, 0)); }
   const int R = r->tabs.nrotations;
@@ -314,8 +396,10 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
                        (const uint8_t *)r->d_relabel);
   } else
     hipLaunchKernelGGL(k_rxb_compact, dim3((g.n_tiles * kRxbCompactLanes + 63) / 64, b->n), dim3(64), 0, sa, A, R, quad, (const uint8_t *)r->d_relabel);
+  if (b->rep_on) hipLaunchKernelGGL(k_rxb_reports, dim3(b->n), dim3(kRxbRepThreads), 0, sa, A);
   LSDR_HIP(hipGetLastError());
   LSDR_HIP(hipMemcpyAsync(b->h_res, b->d_res, b->n * sizeof(rx_seam_result), hipMemcpyDeviceToHost, sa));
+  if (b->rep_on) LSDR_HIP(hipMemcpyAsync(b->h_slots, b->d_slots, b->n * b->rep_pitch * sizeof(rx_meas), hipMemcpyDeviceToHost, sa));
   return LSDR_OK;
 }
 
