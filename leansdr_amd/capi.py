@@ -853,12 +853,71 @@ class RxBatch:
         return st
 
 
-class CaptureBatch:
+class _TailBatch:
+    """What the objects in front of the device-resident FEC tail share (CaptureBatch, HsBatch): a batch of self.n captures through
+    run_async / wait, the TS download, and fetching TS and stage bytes.  A subclass sets _what, its name in error texts, and _c, the
+    prefix of its C entry points (<_c>_wait, _ts_download_async, _ts_wait, _ts_dev, _bytes_dev, _mpeg_dev and _destroy), and hands its
+    handle and its run_async entry point to _attach."""
+
+    def _attach(self, h, run):
+        self.h, self._run = h, run
+        self._res = (CaptureResult * max(self.n, 1))()
+
+    def _fn(self, name):
+        return getattr(lib, f"{self._c}_{name}")
+
+    def _ptrs(self, ptrs):
+        return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in ptrs])
+
+    def close(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def run_async(self, iq_ptrs, n_samples):
+        check(self._run(self.h, self._ptrs(iq_ptrs), int(n_samples)))
+
+    def wait(self, results=True):
+        check(self._fn("wait")(self.h, self._res if results else None))
+        return [r.as_dict() for r in self._res[:self.n]] if results else None
+
+    def ts_download_async(self, host_ptrs, cap_bytes):
+        check(self._fn("ts_download_async")(self.h, self._ptrs(host_ptrs), int(cap_bytes)))
+
+    def ts_wait(self):
+        check(self._fn("ts_wait")(self.h))
+
+    def _fetch(self, ptr, n, sync=True):
+        """n bytes at the device pointer ptr (host; sync=False: there after the caller's ctx.sync())."""
+        a = np.empty(int(n), np.uint8)
+        if n:
+            if ptr is None:
+                raise LsdrError(f"{self._what}: no such capture")
+            check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(a), ptr, int(n)))
+            if sync:
+                self.ctx.sync()
+        return a
+
+    def decode(self, iq_ptrs, n_samples):
+        """One batch, synchronously: (results, [TS bytes per capture])."""
+        self.run_async(iq_ptrs, n_samples)
+        res = self.wait()
+        out = [self._fetch(self._fn("ts_dev")(self.h, i), r["ts_packets"] * 188, sync=False) for i, r in enumerate(res)]
+        self.ctx.sync()
+        return res, [a.tobytes() for a in out]
+
+    def stage_bytes(self, i, which, n):
+        """The first n bytes in front of mpeg_sync ("deconv") or behind it ("mpeg") of capture i after a run (host)."""
+        return self._fetch(self._fn("bytes_dev" if which == "deconv" else "mpeg_dev")(self.h, int(i)), n)
+
+
+class CaptureBatch(_TailBatch):
     """lsdr_capture_batch: B independent cu8 captures, each from its first sample to TS (leandvb's default `--u8` graph per capture),
     in shared launches with the counts on the device.  viterbi=True (or a dict of lsdr_capture_viterbi_cfg fields): the `--viterbi` graph —
     soft symbols, viterbi_sync, mpeg_sync without a deconvolver.  in_format / in_scale (lsdr_capture_input_cfg): captures of IN_CS8,
     IN_CU16, IN_CS16 or IN_CF32 items, converted (and multiplied by in_scale) in the kernels' loads — leandvb's --s8 / --u16 / --s16 /
     --f32 --float-scale; the converted samples must have an RMS near 75 (the level contract, include/lsdr_hip.h)."""
+    _c, _what = "lsdr_capture_batch", "capture batch"
 
     def __init__(self, ctx, n_captures, max_samples, omega, fec=FEC12, anf=1, tile_len=0, tile_warmup=0, notch_k=0.0, notch_decimation=0,
                  unlocked_window=0, aux_cus=0, viterbi=None, in_format=IN_CU8, in_scale=0.0, reports=0):
@@ -884,51 +943,13 @@ class CaptureBatch:
             check(lib.lsdr_capture_batch_create_viterbi(ctx.h, C.byref(cfg), C.byref(vcfg), C.byref(h)))
         else:
             check(lib.lsdr_capture_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
-        self.h = h
-        self._res = (CaptureResult * self.n)()
+        self._attach(h, lib.lsdr_capture_any_run_async if self._any else lib.lsdr_capture_batch_run_async)
         if reports:
             try:
                 self.set_reports(reports)
             except Exception:
                 self.close()
                 raise
-
-    def close(self):
-        if self.h:
-            lib.lsdr_capture_batch_destroy(self.h)
-            self.h = None
-
-    def run_async(self, iq_ptrs, n_samples):
-        ins = (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs])
-        if self._any:
-            check(lib.lsdr_capture_any_run_async(self.h, ins, int(n_samples)))
-        else:
-            check(lib.lsdr_capture_batch_run_async(self.h, ins, int(n_samples)))
-
-    def wait(self, results=True):
-        check(lib.lsdr_capture_batch_wait(self.h, self._res if results else None))
-        return [r.as_dict() for r in self._res] if results else None
-
-    def ts_download_async(self, host_ptrs, cap_bytes):
-        outs = (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in host_ptrs])
-        check(lib.lsdr_capture_batch_ts_download_async(self.h, outs, int(cap_bytes)))
-
-    def ts_wait(self):
-        check(lib.lsdr_capture_batch_ts_wait(self.h))
-
-    def decode(self, iq_ptrs, n_samples):
-        """One batch, synchronously: (results, [TS bytes per capture])."""
-        self.run_async(iq_ptrs, n_samples)
-        res = self.wait()
-        out = []
-        for i, r in enumerate(res):
-            nb = r["ts_packets"] * 188
-            a = np.empty(nb, np.uint8)
-            if nb:
-                check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(a), lib.lsdr_capture_batch_ts_dev(self.h, i), nb))
-            out.append(a)
-        self.ctx.sync()
-        return res, [a.tobytes() for a in out]
 
     def words(self, i, nsym):
         """The packed decisions of capture i after a run, unpacked (host)."""
@@ -958,14 +979,6 @@ class CaptureBatch:
         st = CaptureViterbiStats()
         check(lib.lsdr_capture_batch_viterbi_stats(self.h, int(i), C.byref(st)))
         return st.as_dict()
-
-    def stage_bytes(self, i, which, n):
-        fn = lib.lsdr_capture_batch_bytes_dev if which == "deconv" else lib.lsdr_capture_batch_mpeg_dev
-        a = np.empty(int(n), np.uint8)
-        if n:
-            check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(a), fn(self.h, i), int(n)))
-            self.ctx.sync()
-        return a
 
     def bins(self, i, cap=4096):
         b = (C.c_int * cap)()
@@ -1001,10 +1014,11 @@ class CaptureBatch:
         return ms.value, n.value
 
 
-class HsBatch:
+class HsBatch(_TailBatch):
     """lsdr_hs_batch: B independent cu8 captures, each from its first sample to TS by leandvb's `--hs` graph (fast_qpsk_receiver →
     dvb_deconvol_sync → mpeg_sync(fastlock) → deinterleaver → rs_decoder → derandomizer), in shared launches with every count on the
     device.  freq: the receiver's frequency bias in cycles per sample (FastQpsk's convention)."""
+    _c, _what = "lsdr_hs_batch", "hs batch"
 
     def __init__(self, ctx, n_captures, max_samples, omega, freq=0.0, allow_drift=0, fastlock=0, tile_len=0, tile_warmup=0):
         self.ctx, self.n = ctx, int(n_captures)
@@ -1013,43 +1027,7 @@ class HsBatch:
         cfg.allow_drift, cfg.fastlock, cfg.tile_len, cfg.tile_warmup = int(allow_drift), int(fastlock), tile_len, tile_warmup
         h = vp()
         check(lib.lsdr_hs_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
-        self.h = h
-        self._res = (CaptureResult * max(self.n, 1))()
-
-    def close(self):
-        if self.h:
-            lib.lsdr_hs_batch_destroy(self.h)
-            self.h = None
-
-    def run_async(self, iq_ptrs, n_samples):
-        ins = (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs])
-        check(lib.lsdr_hs_batch_run_async(self.h, ins, int(n_samples)))
-
-    def wait(self, results=True):
-        check(lib.lsdr_hs_batch_wait(self.h, self._res if results else None))
-        return [r.as_dict() for r in self._res][:self.n] if results else None
-
-    def ts_download_async(self, host_ptrs, cap_bytes):
-        outs = (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in host_ptrs])
-        check(lib.lsdr_hs_batch_ts_download_async(self.h, outs, int(cap_bytes)))
-
-    def ts_wait(self):
-        check(lib.lsdr_hs_batch_ts_wait(self.h))
-
-    def _fetch(self, ptr, n):
-        a = np.empty(int(n), np.uint8)
-        if n:
-            if ptr is None:
-                raise LsdrError("hs batch: no such capture")
-            check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(a), ptr, int(n)))
-            self.ctx.sync()
-        return a
-
-    def decode(self, iq_ptrs, n_samples):
-        """One batch, synchronously: (results, [TS bytes per capture])."""
-        self.run_async(iq_ptrs, n_samples)
-        res = self.wait()
-        return res, [self._fetch(lib.lsdr_hs_batch_ts_dev(self.h, i), r["ts_packets"] * 188).tobytes() for i, r in enumerate(res)]
+        self._attach(h, lib.lsdr_hs_batch_run_async)
 
     def symbols_ptr(self, i):
         """Device pointer of capture i's hard symbols, one per byte (None for i out of range)."""
@@ -1058,10 +1036,6 @@ class HsBatch:
     def symbols(self, i, n):
         """The first n hard symbols of capture i after a run (host)."""
         return self._fetch(self.symbols_ptr(i), n)
-
-    def stage_bytes(self, i, which, n):
-        fn = lib.lsdr_hs_batch_bytes_dev if which == "deconv" else lib.lsdr_hs_batch_mpeg_dev
-        return self._fetch(fn(self.h, int(i)), n)
 
 
 def hs2_pack(symbols, offset=0):

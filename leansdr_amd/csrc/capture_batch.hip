@@ -24,11 +24,8 @@ struct lsdr_capture_batch {
   lsdr_capture_batch_cfg cfg;
   lsdr_rxb *rx;
   lsdr_tail *tail;
-  hipEvent_t ev_done, ev_dl;
-  hipStream_t dl;                  // TS downloads
-  bool in_flight, dl_pending, waited;
+  bool in_flight;
   size_t consumed;
-  std::vector<unsigned long long> n_ts;
   // the Viterbi engine (vb != null)
   lsdr_viterbi_batch *vb;
   size_t soft_cap, byte_cap;
@@ -59,7 +56,6 @@ extern "C" {
 
 void lsdr_capture_batch_destroy(lsdr_capture_batch *b) {
   if (!b) return;
-  if (b->dl) { (void)hipStreamSynchronize(b->dl); }
   if (b->ctx) (void)hipStreamSynchronize(b->ctx->stream);
   if (b->ctx_aux) (void)hipStreamSynchronize(b->ctx_aux->stream);
   lsdr_viterbi_batch_destroy(b->vb);
@@ -67,9 +63,6 @@ void lsdr_capture_batch_destroy(lsdr_capture_batch *b) {
   lsdr_rxb_destroy(b->rx);
   if (b->ctx_aux) lsdr_ctx_destroy(b->ctx_aux);
   if (b->own_main) lsdr_ctx_destroy(b->own_main);
-  if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-  if (b->ev_dl) (void)hipEventDestroy(b->ev_dl);
-  if (b->dl) (void)hipStreamDestroy(b->dl);
   delete b;
 }
 
@@ -119,7 +112,7 @@ static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi
     LSDR_TRY(lsdr_viterbi_batch_create(ct, LSDR_QPSK, vrate, b->cfg.n_captures, b->soft_cap, &b->vb));
     if (vcfg->resync_period > 0) LSDR_TRY(lsdr_viterbi_batch_set_resync_period(b->vb, vcfg->resync_period));
     // viterbi_sync writes less than two bits per QPSK symbol at any rate
-    LSDR_TRY(lsdr_tail_create_ex(ct, (unsigned)b->cfg.n_captures, b->soft_cap, b->cfg.fec, window, 1, b->soft_cap / 4 + 64, &b->tail));
+    LSDR_TRY(lsdr_tail_create_ex(ct, (unsigned)b->cfg.n_captures, b->soft_cap, b->cfg.fec, window, 1, b->soft_cap / 4 + 64, "capture_batch", &b->tail));
     b->byte_cap = lsdr_tail_byte_cap(b->tail);
     const void *counts = lsdr_rxb_results_dev(b->rx, &stride);
     LSDR_TRY(lsdr_tail_bind(b->tail, nullptr, counts, stride));
@@ -129,16 +122,12 @@ static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi
   } else {
     LSDR_TRY(lsdr_rxb_create_in(c, &b->cfg, 0, 1.0f, b->in_format, b->in_scale, &b->rx));
     const size_t sym_cap = lsdr_rxb_words_cap(b->rx) * 16;
-    LSDR_TRY(lsdr_tail_create(ct, (unsigned)b->cfg.n_captures, sym_cap, b->cfg.fec, window, &b->tail));
+    LSDR_TRY(lsdr_tail_create_ex(ct, (unsigned)b->cfg.n_captures, sym_cap, b->cfg.fec, window, 0, 0, "capture_batch", &b->tail));
     std::vector<const uint32_t *> words(b->cfg.n_captures);
     for (int i = 0; i < b->cfg.n_captures; ++i) words[i] = lsdr_rxb_words(b->rx, (unsigned)i);
     const void *counts = lsdr_rxb_results_dev(b->rx, &stride);
     LSDR_TRY(lsdr_tail_bind(b->tail, words.data(), counts, stride));
   }
-  LSDR_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-  LSDR_HIP(hipEventCreateWithFlags(&b->ev_dl, hipEventDisableTiming));
-  LSDR_HIP(hipStreamCreateWithFlags(&b->dl, hipStreamNonBlocking));
-  b->n_ts.assign(b->cfg.n_captures, 0);
   return LSDR_OK;
 }
 
@@ -179,12 +168,11 @@ int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev,
   if (b->vb) {
     const std::vector<unsigned long long> zero(b->cfg.n_captures, 0ull);
     LSDR_TRY(capture_batch_viterbi_round(b, true, zero, zero, zero));
-    b->in_flight = true; b->waited = false;
-    return LSDR_OK;
+    lsdr_tail_stale(b->tail);                                           // (the tail is launched in wait)
+  } else {
+    LSDR_TRY(lsdr_tail_launch(b->tail));
   }
-  LSDR_TRY(lsdr_tail_launch(b->tail, b->dl_pending ? b->ev_dl : nullptr));
-  LSDR_HIP(hipEventRecord(b->ev_done, (b->ctx_aux ? b->ctx_aux : b->ctx)->stream));
-  b->in_flight = true; b->waited = false;
+  b->in_flight = true;
   return LSDR_OK;
 }
 
@@ -224,20 +212,13 @@ int lsdr_capture_batch_wait(lsdr_capture_batch *b, lsdr_capture_result *results)
       LSDR_TRY(capture_batch_viterbi_round(b, false, total, done, bytes));
     }
     LSDR_TRY(lsdr_tail_set_bytes(b->tail, bytes.data(), align.data()));
-    LSDR_TRY(lsdr_tail_launch(b->tail, b->dl_pending ? b->ev_dl : nullptr));
-    LSDR_HIP(hipEventRecord(b->ev_done, (b->ctx_aux ? b->ctx_aux : b->ctx)->stream));
+    LSDR_TRY(lsdr_tail_launch(b->tail));
   }
-  LSDR_HIP(hipEventSynchronize(b->ev_done));
-  b->in_flight = false; b->waited = true;
-  const lsdr_tail_result *tr = lsdr_tail_results(b->tail);
-  for (int i = 0; i < b->cfg.n_captures; ++i) {
-    b->n_ts[i] = tr[i].n_ts;
-    if (!results) continue;
+  LSDR_TRY(lsdr_tail_wait(b->tail, results));
+  b->in_flight = false;
+  for (int i = 0; results && i < b->cfg.n_captures; ++i) {
     lsdr_capture_result &r = results[i];
-    memset(&r, 0, sizeof(r));
-    r.ts_packets = tr[i].n_ts; r.rs_packets = tr[i].n_rs; r.rs_bit_errors = tr[i].rs_bit_errors; r.symbols = tr[i].symbols;
-    r.samples = b->consumed; r.bytes_deconv = tr[i].bytes_deconv; r.bytes_mpeg = tr[i].bytes_mpeg; r.first_lock_byte = tr[i].first_lock_byte;
-    r.next_sync_calls = tr[i].next_sync_calls; r.locked = tr[i].locked_at_end; r.alignment = tr[i].alignment; r.bitphase = tr[i].bitphase;
+    r.samples = b->consumed;
     r.tiles = lsdr_rxb_tiles(b->rx);
     unsigned long long tot = 0; unsigned d = 0, m = 0, bad = 0;
     LSDR_TRY(lsdr_rxb_seam_stats(b->rx, (unsigned)i, &tot, &d, &m, &bad));
@@ -247,23 +228,13 @@ int lsdr_capture_batch_wait(lsdr_capture_batch *b, lsdr_capture_result *results)
 }
 
 int lsdr_capture_batch_ts_download_async(lsdr_capture_batch *b, uint8_t *const *ts_host, size_t cap_bytes) {
-  LSDR_ARG(b && ts_host);
-  if (!b->waited) { lsdr_set_error("capture_batch: TS download before lsdr_capture_batch_wait"); return LSDR_E_ARG; }
-  for (int i = 0; i < b->cfg.n_captures; ++i) {
-    const size_t bytes = (size_t)b->n_ts[i] * 188;
-    if (bytes > cap_bytes) { lsdr_set_error("capture_batch: capture %d has %zu TS bytes, the host buffer %zu", i, bytes, cap_bytes); return LSDR_E_ARG; }
-    if (bytes) LSDR_HIP(hipMemcpyAsync(ts_host[i], lsdr_tail_ts_dev(b->tail, (unsigned)i), bytes, hipMemcpyDeviceToHost, b->dl));
-  }
-  LSDR_HIP(hipEventRecord(b->ev_dl, b->dl));
-  b->dl_pending = true;
-  return LSDR_OK;
+  LSDR_ARG(b);
+  return lsdr_tail_ts_download_async(b->tail, ts_host, cap_bytes);
 }
 
 int lsdr_capture_batch_ts_wait(lsdr_capture_batch *b) {
   LSDR_ARG(b);
-  if (b->dl_pending) LSDR_HIP(hipEventSynchronize(b->ev_dl));
-  b->dl_pending = false;
-  return LSDR_OK;
+  return lsdr_tail_ts_wait(b->tail);
 }
 
 static bool capture_index_ok(const lsdr_capture_batch *b, int i) { return b && i >= 0 && i < b->cfg.n_captures; }
@@ -314,7 +285,7 @@ int lsdr_capture_reports_get(lsdr_capture_batch *b, int i, lsdr_capture_report *
   lsdr_rxb_report fin;
   size_t have = 0;
   LSDR_TRY(lsdr_rxb_reports(b->rx, (unsigned)i, &slots, &have, &fin));
-  if (!b->waited) have = 0;                                                // (no batch yet)
+  if (!lsdr_tail_waited(b->tail)) have = 0;                                // (no batch yet)
   for (size_t q = 0; q < have && q < cap; ++q) out[q] = capture_report(slots[q]);
   *n = have;
   if (last) *last = capture_report(fin);

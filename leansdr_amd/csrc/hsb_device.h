@@ -24,7 +24,7 @@
 #ifndef LSDR_HSB_DEVICE_H
 #define LSDR_HSB_DEVICE_H
 
-struct hsb_rec {                   // per capture, device memory; copied to pinned memory behind the tail
+struct hsb_rec {                   // per capture, device memory; copied to pinned memory in front of the tail (which only reads it)
   unsigned long long total;        // symbols in the capture's array (the tail's `nsym`)
   unsigned ndup, nmiss, nbad, pad;
   unsigned long long chunks;       // deconvolver chunks decoded

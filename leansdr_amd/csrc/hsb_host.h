@@ -1,6 +1,6 @@
 // leansdr_amd/csrc/hsb_host.h — host side of lsdr_hs_batch (hsb_device.h); included at the end of hs.hip.  The FEC tail is fec.hip's
 // lsdr_tail in its form without deconvol_sync, with mpeg_sync constructed as leandvb --hs constructs it (fastlock = true, resync_period).
-// run_async queues everything on the caller's context stream and reads nothing back; wait is one event synchronisation.
+// run_async queues everything on the caller's context stream and reads nothing back; wait is one event synchronisation (the tail's).
 #ifndef LSDR_HSB_HOST_H
 #define LSDR_HSB_HOST_H
 
@@ -15,12 +15,9 @@ struct lsdr_hs_batch {
   const unsigned char **d_in, **h_in;        // [B] capture pointers: device copy, pinned staging
   unsigned char **d_bytes;
   hsb_rec *d_rec, *h_rec;                    // h_rec pinned
-  hipEvent_t ev_done, ev_dl;
-  hipStream_t dl;                            // TS downloads
-  bool in_flight, dl_pending, waited;
+  bool in_flight;
   int lds_rect;                              // tile kernel with the rect table in LDS: 1 / 0 forced, −1 by the size of the run
   size_t consumed; unsigned tiles;
-  std::vector<unsigned long long> n_ts;
   std::vector<void *> owned;
 };
 
@@ -71,7 +68,7 @@ static int hsb_build(lsdr_hs_batch *b) {
   const size_t byte_room = sym_cap / 8 + 64;
   const unsigned P = cfg.fastlock ? 1u : 32u;                            // leandvb.cc:853, 863
 
-  LSDR_TRY(lsdr_tail_create_ex(c, (unsigned)B, sym_cap, LSDR_FEC12, 8192, 1, byte_room, &b->tail));
+  LSDR_TRY(lsdr_tail_create_ex(c, (unsigned)B, sym_cap, LSDR_FEC12, 8192, 1, byte_room, "hs_batch", &b->tail));
   LSDR_TRY(lsdr_tail_set_mpeg_sync(b->tail, 1, (int)P));
 
   std::vector<unsigned> polar(65536);
@@ -141,10 +138,6 @@ static int hsb_build(lsdr_hs_batch *b) {
   const char *e = getenv("LSDR_HSB_LDS_RECT");
   b->lds_rect = e && *e ? (atoi(e) != 0 ? 1 : 0) : -1;
   LSDR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_hsb_tiles_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2));
-  LSDR_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-  LSDR_HIP(hipEventCreateWithFlags(&b->ev_dl, hipEventDisableTiming));
-  LSDR_HIP(hipStreamCreateWithFlags(&b->dl, hipStreamNonBlocking));
-  b->n_ts.assign(B, 0);
   return LSDR_OK;
 }
 
@@ -152,15 +145,11 @@ extern "C" {
 
 void lsdr_hs_batch_destroy(lsdr_hs_batch *b) {
   if (!b) return;
-  if (b->dl) (void)hipStreamSynchronize(b->dl);
   (void)hipStreamSynchronize(b->ctx->stream);
   lsdr_tail_destroy(b->tail);
   for (void *p : b->owned) (void)hipFree(p);
   if (b->h_in) (void)hipHostFree(b->h_in);
   if (b->h_rec) (void)hipHostFree(b->h_rec);
-  if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-  if (b->ev_dl) (void)hipEventDestroy(b->ev_dl);
-  if (b->dl) (void)hipStreamDestroy(b->dl);
   delete b;
 }
 
@@ -209,28 +198,22 @@ int lsdr_hs_batch_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, siz
   hipLaunchKernelGGL(k_hsb_score, dim3(wide, B), dim3(256), 0, c->stream, A);
   hipLaunchKernelGGL(k_hsb_decode, dim3(wide, B), dim3(256), 0, c->stream, A);
   LSDR_HIP(hipGetLastError());
-  LSDR_TRY(lsdr_tail_launch(b->tail, b->dl_pending ? b->ev_dl : nullptr));
+  // the records go to the host in front of the tail, whose kernels only read them: the tail's "batch done" event is behind everything wait reads
   LSDR_HIP(hipMemcpyAsync(b->h_rec, b->d_rec, B * sizeof(hsb_rec), hipMemcpyDeviceToHost, c->stream));
-  LSDR_HIP(hipEventRecord(b->ev_done, c->stream));
+  LSDR_TRY(lsdr_tail_launch(b->tail));
   b->consumed = chunks * kChunk; b->tiles = n_tiles;
-  b->in_flight = true; b->waited = false;
+  b->in_flight = true;
   return LSDR_OK;
 }
 
 int lsdr_hs_batch_wait(lsdr_hs_batch *b, lsdr_capture_result *results) {
   LSDR_ARG(b);
   if (!b->in_flight) { lsdr_set_error("hs_batch: no batch in flight"); return LSDR_E_ARG; }
-  LSDR_HIP(hipEventSynchronize(b->ev_done));
-  b->in_flight = false; b->waited = true;
-  const lsdr_tail_result *tr = lsdr_tail_results(b->tail);
-  for (int i = 0; i < b->cfg.n_captures; ++i) {
-    b->n_ts[i] = tr[i].n_ts;
-    if (!results) continue;
+  LSDR_TRY(lsdr_tail_wait(b->tail, results));
+  b->in_flight = false;
+  for (int i = 0; results && i < b->cfg.n_captures; ++i) {
     lsdr_capture_result &r = results[i];
-    memset(&r, 0, sizeof(r));
-    r.ts_packets = tr[i].n_ts; r.rs_packets = tr[i].n_rs; r.rs_bit_errors = tr[i].rs_bit_errors; r.symbols = tr[i].symbols;
-    r.samples = b->consumed; r.bytes_deconv = tr[i].bytes_deconv; r.bytes_mpeg = tr[i].bytes_mpeg; r.first_lock_byte = tr[i].first_lock_byte;
-    r.next_sync_calls = tr[i].next_sync_calls; r.locked = tr[i].locked_at_end; r.alignment = tr[i].alignment; r.bitphase = tr[i].bitphase;
+    r.samples = b->consumed;
     r.tiles = b->tiles;
     r.seam_dup = b->h_rec[i].ndup; r.seam_miss = b->h_rec[i].nmiss; r.seam_bad = b->h_rec[i].nbad;
   }
@@ -238,23 +221,13 @@ int lsdr_hs_batch_wait(lsdr_hs_batch *b, lsdr_capture_result *results) {
 }
 
 int lsdr_hs_batch_ts_download_async(lsdr_hs_batch *b, uint8_t *const *ts_host, size_t cap_bytes) {
-  LSDR_ARG(b && ts_host);
-  if (!b->waited) { lsdr_set_error("hs_batch: TS download before lsdr_hs_batch_wait"); return LSDR_E_ARG; }
-  for (int i = 0; i < b->cfg.n_captures; ++i) {
-    const size_t bytes = (size_t)b->n_ts[i] * 188;
-    if (bytes > cap_bytes) { lsdr_set_error("hs_batch: capture %d has %zu TS bytes, the host buffer %zu", i, bytes, cap_bytes); return LSDR_E_ARG; }
-    if (bytes) LSDR_HIP(hipMemcpyAsync(ts_host[i], lsdr_tail_ts_dev(b->tail, (unsigned)i), bytes, hipMemcpyDeviceToHost, b->dl));
-  }
-  LSDR_HIP(hipEventRecord(b->ev_dl, b->dl));
-  b->dl_pending = true;
-  return LSDR_OK;
+  LSDR_ARG(b);
+  return lsdr_tail_ts_download_async(b->tail, ts_host, cap_bytes);
 }
 
 int lsdr_hs_batch_ts_wait(lsdr_hs_batch *b) {
   LSDR_ARG(b);
-  if (b->dl_pending) LSDR_HIP(hipEventSynchronize(b->ev_dl));
-  b->dl_pending = false;
-  return LSDR_OK;
+  return lsdr_tail_ts_wait(b->tail);
 }
 
 static bool hsb_index_ok(const lsdr_hs_batch *b, int i) { return b && i >= 0 && i < b->cfg.n_captures; }

@@ -92,10 +92,7 @@ int lsdr_fir_stream_iv_launch(lsdr_ctx *c, const void *in, size_t n_in, lsdr_cf3
 // ---- capture batch (capture_batch.hip): its two halves
 // cstln_receiver.hip (rxb_host.h): the front end — auto_notch + cstln_receiver of every capture in shared launches, packed decisions out
 struct lsdr_rxb;
-int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **out);
-int lsdr_rxb_create_ex(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, lsdr_rxb **out);
 int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, int in_format, float in_scale, lsdr_rxb **out);
-int lsdr_rxb_in_format(const lsdr_rxb *b);
 void lsdr_rxb_destroy(lsdr_rxb *b);
 int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t *consumed, hipStream_t aux = nullptr);
 const uint32_t *lsdr_rxb_words(const lsdr_rxb *b, unsigned i);
@@ -105,7 +102,6 @@ size_t lsdr_rxb_soft_cap(const lsdr_rxb *b);
 const unsigned long long *lsdr_rxb_counts_dev(const lsdr_rxb *b);
 const void *lsdr_rxb_results_dev(const lsdr_rxb *b, size_t *stride);
 unsigned lsdr_rxb_tiles(const lsdr_rxb *b);
-unsigned lsdr_rxb_detects(const lsdr_rxb *b);
 int lsdr_rxb_bins(lsdr_rxb *b, unsigned i, int *bins, unsigned cap, unsigned *n);
 int lsdr_rxb_seam_stats(lsdr_rxb *b, unsigned i, unsigned long long *total, unsigned *dup, unsigned *miss, unsigned *bad);
 int lsdr_rxb_tile_time(lsdr_rxb *b, int enable, float *avg_ms, unsigned *launches);
@@ -115,23 +111,22 @@ struct lsdr_rxb_report { float freqw, est_insp, est_sp, est_ep, a; unsigned tile
 int lsdr_rxb_set_reports(lsdr_rxb *b, unsigned long long period_samples);
 int lsdr_rxb_reports_on(const lsdr_rxb *b);
 int lsdr_rxb_reports(const lsdr_rxb *b, unsigned i, const lsdr_rxb_report **slots, size_t *n, lsdr_rxb_report *last);
-// fec.hip (tail_host.h): the FEC tail of every capture, counts on the device
+// fec.hip (tail_host.h): the FEC tail of every capture, counts on the device, with its output side — the wait for a batch, the result
+// records and the TS download.  who: the owner's prefix in error texts ("capture_batch" / "hs_batch").
 struct lsdr_tail;
-struct lsdr_tail_result {          // = tail_device.h's tail_result
-  unsigned long long n_ts, n_rs, rs_bit_errors, symbols, bytes_deconv, bytes_mpeg;
-  unsigned next_sync_calls, locked_at_end, alignment, bitphase;
-  unsigned long long first_lock_byte;
-};
-int lsdr_tail_create(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, lsdr_tail **out);
-int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, int nodeconv, size_t bytes_per_capture, lsdr_tail **out);
+int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, int nodeconv, size_t bytes_per_capture, const char *who,
+                        lsdr_tail **out);
 int lsdr_tail_set_bytes(lsdr_tail *t, const unsigned long long *bytes, const unsigned *alignment);
 size_t lsdr_tail_byte_cap(const lsdr_tail *t);
 void lsdr_tail_destroy(lsdr_tail *t);
 int lsdr_tail_bind(lsdr_tail *t, const uint32_t *const *words, const void *counts_dev, size_t count_stride);
-int lsdr_tail_launch(lsdr_tail *t, hipEvent_t before_ts);
-const lsdr_tail_result *lsdr_tail_results(const lsdr_tail *t);
+int lsdr_tail_launch(lsdr_tail *t);                                       // … and records "batch done" behind the last kernel
+int lsdr_tail_wait(lsdr_tail *t, lsdr_capture_result *results);           // fills the tail's fields; samples, tiles, seam_* are the owner's
+bool lsdr_tail_waited(const lsdr_tail *t);                                // between lsdr_tail_wait and the next launch or lsdr_tail_stale
+void lsdr_tail_stale(lsdr_tail *t);                                       // clears it ahead of a launch that comes later
+int lsdr_tail_ts_download_async(lsdr_tail *t, uint8_t *const *ts_host, size_t cap_bytes);
+int lsdr_tail_ts_wait(lsdr_tail *t);
 const uint8_t *lsdr_tail_ts_dev(const lsdr_tail *t, unsigned i);
-size_t lsdr_tail_ts_cap(const lsdr_tail *t);
 const uint8_t *lsdr_tail_bytes_dev(const lsdr_tail *t, unsigned i);
 const uint8_t *lsdr_tail_mpeg_dev(const lsdr_tail *t, unsigned i);
 // the tail without deconvol_sync (nodeconv) behind a producer that stays on the device (hs.hip's lsdr_hs_batch): mpeg_sync's public members

@@ -423,7 +423,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
   unsigned *const hcol = cap.hstage + j;
   // SOFT: body symbol k goes to byte 4·(k·hpitch + j) of sstage (one row of `hpitch` dwords per symbol step: the 64 lanes of the wavefront
   // are 64 consecutive tiles and write 64 consecutive dwords; a capture's staging is below 4 GiB, so k and 4·hpitch fit 24 bits:
-  // lsdr_rxb_create_ex)
+  // lsdr_rxb_create_in)
   const unsigned srow = 4u * (unsigned)cap.hpitch;
   // SOFT: the amplitude the COSTS are taken at.  A cost is proportional to the sampled point's amplitude, so the soft records need the
   // gain the serial receiver has at this tile — its power estimate is an average over the last hundred chunks (kest = 0.01 per chunk,

@@ -68,15 +68,9 @@ static rxb_geom rxb_geometry(const lsdr_rxb *b, size_t n_samples) {
   return g;
 }
 
-int lsdr_rxb_create(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, lsdr_rxb **out) { return lsdr_rxb_create_ex(c, cfg, 0, 1.0f, out); }
-
 // soft != 0: lsdr_softsymbol records out (rxb_device.h's soft tiles); pll_adjustment: cstln_receiver::pll_adjustment (sdr.h:777: divides
 // freq_beta only), 1 in leandvb's default graph, 6 behind viterbi_sync (leandvb.cc:498-501) — given here as the factor 1/6
-int lsdr_rxb_create_ex(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, lsdr_rxb **out) {
-  return lsdr_rxb_create_in(c, cfg, soft, pll_adjustment, LSDR_IN_CU8, 0.f, out);
-}
-
-// in_format / in_scale: lsdr_capture_input_cfg (checked here).  cu8 without a scale is the object of lsdr_rxb_create_ex: its own kernels.
+// in_format / in_scale: lsdr_capture_input_cfg (checked here).  cu8 without a scale has its own kernels.
 int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, int in_format, float in_scale, lsdr_rxb **out) {
   LSDR_ARG(c && cfg && out && cfg->n_captures >= 1 && cfg->n_captures <= 4096 && cfg->max_samples >= 4096);
   LSDR_ARG(cfg->anf == 0 || cfg->anf == 1);
@@ -321,7 +315,6 @@ static rxb_kernel_t rxb_kernel_pre(int kind) {
 static rxb_dump_kernel_t rxb_kernel_dump(int kind) {
   return kind == kRxbS8 ? k_rxb_notch_dump<kRxbS8> : kind == kRxb16 ? k_rxb_notch_dump<kRxb16> : kind == kRxbF32 ? k_rxb_notch_dump<kRxbF32> : k_rxb_notch_dump<kRxbU8>;
 }
-int lsdr_rxb_in_format(const lsdr_rxb *b) { return b ? b->in_format : -1; }
 
 // Queues the whole front end of a batch: detect chain, estimator pre-pass, tiles, seam pass, compaction.  aux == nullptr: everything on
 // the context's stream.  aux: the TILES on the context's stream, everything else on `aux` (the caller's stream for the memory-bound
@@ -412,7 +405,6 @@ const unsigned long long *lsdr_rxb_counts_dev(const lsdr_rxb *b) { return b ? b-
 // device array [n]: .total = packed decisions of capture i after the launch (struct rx_seam_result: 8-byte total first)
 const void *lsdr_rxb_results_dev(const lsdr_rxb *b, size_t *stride) { if (stride) *stride = sizeof(rx_seam_result); return b ? b->d_res : nullptr; }
 unsigned lsdr_rxb_tiles(const lsdr_rxb *b) { return b ? b->n_tiles : 0; }
-unsigned lsdr_rxb_detects(const lsdr_rxb *b) { return b ? b->n_det : 0; }
 // debugging / tests: the detected bins of capture i (synchronous)
 int lsdr_rxb_bins(lsdr_rxb *b, unsigned i, int *bins, unsigned cap, unsigned *n) {
   LSDR_ARG(b && i < b->n && n);

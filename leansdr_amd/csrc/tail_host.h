@@ -1,5 +1,6 @@
 // leansdr_amd/csrc/tail_host.h — host side of the device-resident FEC tail (tail_device.h); included at the end of fec.hip.
-// Internal API (lsdr_internal.h) of lsdr_capture_batch (capture_batch.hip).
+// Internal API (lsdr_internal.h) of lsdr_capture_batch (capture_batch.hip) and lsdr_hs_batch (hsb_host.h).  The tail owns its output side:
+// the "batch done" event behind its last kernel, the result records, and the TS download on a stream of its own.
 #ifndef LSDR_TAIL_HOST_H
 #define LSDR_TAIL_HOST_H
 
@@ -16,6 +17,10 @@ struct lsdr_tail {
   std::vector<void *> owned;
   bool nodeconv;                    // the Viterbi engine's tail: `bytes` is filled by viterbi_sync (k_tail_acquire_bytes)
   tail_vit *h_vit, *d_vit;          // nodeconv: [n] pinned staging and device records
+  const char *who;                  // the owner's prefix in error texts ("capture_batch" / "hs_batch")
+  hipEvent_t ev_done, ev_dl;        // behind the last kernel of a launch; behind the last TS download
+  hipStream_t dl;                   // TS downloads
+  bool dl_pending, waited;          // waited: between lsdr_tail_wait and the next launch — results and TS are stable
 };
 
 static int tail_alloc(lsdr_tail *t, void **p, size_t bytes) {
@@ -24,22 +29,23 @@ static int tail_alloc(lsdr_tail *t, void **p, size_t bytes) {
   return LSDR_OK;
 }
 
-int lsdr_tail_create(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, lsdr_tail **out) {
-  return lsdr_tail_create_ex(c, n, sym_cap, rate, window, 0, 0, out);
-}
-
-// bytes_per_capture != 0: the tail behind viterbi_sync — no deconvol_sync; every capture's `bytes` buffer takes that many bytes
-int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, int nodeconv, size_t bytes_per_capture, lsdr_tail **out) {
-  LSDR_ARG(c && out && n >= 1 && sym_cap >= 1 && window >= 2048);      // (mpeg_sync's search needs 204·8 + 1 bytes in one call)
+// nodeconv (bytes_per_capture != 0): the tail behind viterbi_sync — no deconvol_sync; every capture's `bytes` buffer takes that many bytes.
+// who: the owner's prefix in error texts (a string literal).
+int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsigned window, int nodeconv, size_t bytes_per_capture, const char *who,
+                        lsdr_tail **out) {
+  LSDR_ARG(c && out && who && n >= 1 && sym_cap >= 1 && window >= 2048);      // (mpeg_sync's search needs 204·8 + 1 bytes in one call)
   LSDR_ARG(!nodeconv || bytes_per_capture >= 1);
   LSDR_HIP(hipSetDevice(c->device));
   lsdr_tail *t = new lsdr_tail();
-  t->ctx = c; t->n = n; t->sym_cap = sym_cap; t->nodeconv = nodeconv != 0; t->h_vit = nullptr; t->d_vit = nullptr;
+  t->ctx = c; t->n = n; t->sym_cap = sym_cap; t->nodeconv = nodeconv != 0; t->h_vit = nullptr; t->d_vit = nullptr; t->who = who;
   *out = t;                                                             // (from here on the caller destroys on error)
+  LSDR_HIP(hipEventCreateWithFlags(&t->ev_done, hipEventDisableTiming));
+  LSDR_HIP(hipEventCreateWithFlags(&t->ev_dl, hipEventDisableTiming));
+  LSDR_HIP(hipStreamCreateWithFlags(&t->dl, hipStreamNonBlocking));
   if (!t->nodeconv) LSDR_TRY(lsdr_deconv_create(c, rate, 0, &t->dec));
   LSDR_TRY(lsdr_derandomizer_create(c, &t->der));
   gf_tables *tab = rs_device_tables(c);
-  if (!tab) { lsdr_set_error("capture_batch: cannot allocate GF tables"); return LSDR_E_NOMEM; }
+  if (!tab) { lsdr_set_error("%s: cannot allocate GF tables", who); return LSDR_E_NOMEM; }
   memset(&t->A, 0, sizeof(t->A));
   if (t->nodeconv) {
     t->byte_cap = (bytes_per_capture + 65536 + 3) & ~(size_t)3;
@@ -91,6 +97,7 @@ int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsig
 
 void lsdr_tail_destroy(lsdr_tail *t) {
   if (!t) return;
+  if (t->dl) (void)hipStreamSynchronize(t->dl);
   (void)hipStreamSynchronize(t->ctx->stream);
   for (void *p : t->owned) (void)hipFree(p);
   (void)hipFree(t->d_caps);
@@ -99,6 +106,9 @@ void lsdr_tail_destroy(lsdr_tail *t) {
   if (t->h_vit) (void)hipHostFree(t->h_vit);
   if (t->dec) lsdr_deconv_destroy(t->dec);
   lsdr_derandomizer_destroy(t->der);
+  if (t->ev_done) (void)hipEventDestroy(t->ev_done);
+  if (t->ev_dl) (void)hipEventDestroy(t->ev_dl);
+  if (t->dl) (void)hipStreamDestroy(t->dl);
   delete t;
 }
 
@@ -113,8 +123,6 @@ int lsdr_tail_bind(lsdr_tail *t, const uint32_t *const *words, const void *count
   return LSDR_OK;
 }
 
-// Queues the tail of every capture on the context's stream.  `before_ts`: an event the kernel that WRITES the TS buffers waits for (the
-// download of the previous batch's TS), or null.
 // nodeconv: what viterbi_sync committed for every capture (bytes already in lsdr_tail_bytes_dev(i)) and its alignment; queued on the
 // context's stream in front of the next lsdr_tail_launch.  The previous launch must have completed (single-buffered staging).
 int lsdr_tail_set_bytes(lsdr_tail *t, const unsigned long long *bytes, const unsigned *alignment) {
@@ -132,7 +140,9 @@ int lsdr_tail_set_mpeg_sync(lsdr_tail *t, int fastlock, int resync_period) {
 }
 lsdr_tail_vit *lsdr_tail_vit_dev(lsdr_tail *t) { return t && t->nodeconv ? reinterpret_cast<lsdr_tail_vit *>(t->d_vit) : nullptr; }
 
-int lsdr_tail_launch(lsdr_tail *t, hipEvent_t before_ts) {
+// Queues the tail of every capture on the context's stream, and the "batch done" event behind it.  The kernel that WRITES the TS buffers
+// waits for a pending download of the previous batch's TS.
+int lsdr_tail_launch(lsdr_tail *t) {
   LSDR_ARG(t);
   lsdr_ctx *c = t->ctx;
   LSDR_HIP(hipSetDevice(c->device));
@@ -154,21 +164,60 @@ int lsdr_tail_launch(lsdr_tail *t, hipEvent_t before_ts) {
   hipLaunchKernelGGL(k_tail_rs, grid, dim3(256), 0, c->stream, t->A);
   hipLaunchKernelGGL(k_tail_derand_scan, one, dim3(1024), 0, c->stream, t->A);
   LSDR_HIP(hipGetLastError());
-  if (before_ts) LSDR_HIP(hipStreamWaitEvent(c->stream, before_ts, 0));
+  if (t->dl_pending) LSDR_HIP(hipStreamWaitEvent(c->stream, t->ev_dl, 0));
   hipLaunchKernelGGL(k_tail_derand_apply, grid, dim3(256), 0, c->stream, t->A);
   LSDR_HIP(hipGetLastError());
+  LSDR_HIP(hipEventRecord(t->ev_done, c->stream));
+  t->waited = false;
   return LSDR_OK;
 }
 
-const lsdr_tail_result *lsdr_tail_results(const lsdr_tail *t) { return t ? reinterpret_cast<const lsdr_tail_result *>(t->h_res) : nullptr; }
+// Waits for the last launch.  results (may be null): every record zeroed, then the tail's fields; samples, tiles and seam_* are the owner's.
+int lsdr_tail_wait(lsdr_tail *t, lsdr_capture_result *results) {
+  LSDR_ARG(t);
+  LSDR_HIP(hipEventSynchronize(t->ev_done));
+  t->waited = true;
+  for (unsigned i = 0; results && i < t->n; ++i) {
+    const tail_result &tr = t->h_res[i];
+    lsdr_capture_result &r = results[i];
+    memset(&r, 0, sizeof(r));
+    r.ts_packets = tr.n_ts; r.rs_packets = tr.n_rs; r.rs_bit_errors = tr.rs_bit_errors; r.symbols = tr.symbols;
+    r.bytes_deconv = tr.bytes_deconv; r.bytes_mpeg = tr.bytes_mpeg; r.first_lock_byte = tr.first_lock_byte;
+    r.next_sync_calls = tr.next_sync_calls; r.locked = tr.locked_at_end; r.alignment = tr.alignment; r.bitphase = tr.bitphase;
+  }
+  return LSDR_OK;
+}
+bool lsdr_tail_waited(const lsdr_tail *t) { return t && t->waited; }
+// a batch is under way in front of the tail (the Viterbi engine launches the tail only in its wait): the last batch's output is no longer current
+void lsdr_tail_stale(lsdr_tail *t) { if (t) t->waited = false; }
+
+// Every capture's TS of the waited-for batch to ts_host[i] (cap_bytes each), on the download stream; the next launch's TS writes wait for it.
+int lsdr_tail_ts_download_async(lsdr_tail *t, uint8_t *const *ts_host, size_t cap_bytes) {
+  LSDR_ARG(t && ts_host);
+  if (!t->waited) { lsdr_set_error("%s: TS download before lsdr_%s_wait", t->who, t->who); return LSDR_E_ARG; }
+  for (unsigned i = 0; i < t->n; ++i) {
+    const size_t bytes = (size_t)t->h_res[i].n_ts * kTS;
+    if (bytes > cap_bytes) { lsdr_set_error("%s: capture %d has %zu TS bytes, the host buffer %zu", t->who, (int)i, bytes, cap_bytes); return LSDR_E_ARG; }
+    if (bytes) LSDR_HIP(hipMemcpyAsync(ts_host[i], t->caps[i].ts, bytes, hipMemcpyDeviceToHost, t->dl));
+  }
+  LSDR_HIP(hipEventRecord(t->ev_dl, t->dl));
+  t->dl_pending = true;
+  return LSDR_OK;
+}
+
+int lsdr_tail_ts_wait(lsdr_tail *t) {
+  LSDR_ARG(t);
+  if (t->dl_pending) LSDR_HIP(hipEventSynchronize(t->ev_dl));
+  t->dl_pending = false;
+  return LSDR_OK;
+}
+
 const uint8_t *lsdr_tail_ts_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].ts : nullptr; }
-size_t lsdr_tail_ts_cap(const lsdr_tail *t) { return t ? t->pk_cap * kTS : 0; }
 // tests: the deconvolved bytes / the mpeg_sync output of capture i (device pointers; counts in the result record)
 size_t lsdr_tail_byte_cap(const lsdr_tail *t) { return t ? t->byte_cap : 0; }
 const uint8_t *lsdr_tail_bytes_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].bytes : nullptr; }
 const uint8_t *lsdr_tail_mpeg_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].mpeg : nullptr; }
 
-static_assert(sizeof(lsdr_tail_result) == sizeof(tail_result), "lsdr_internal.h mirrors tail_device.h's result record");
 static_assert(sizeof(lsdr_tail_vit) == sizeof(tail_vit) && offsetof(lsdr_tail_vit, alignment) == offsetof(tail_vit, alignment),
               "lsdr_internal.h mirrors tail_device.h's tail_vit");
 

@@ -1,0 +1,166 @@
+"""Shared helpers of the batch decoders' tests (lsdr_capture_batch in its engines and formats, lsdr_hs_batch): the synthetic captures, the
+reference binary's TS for them, the rule a batch's TS is compared with it by, the input variants of the exactness tests, and the FEC tail
+driven by the host as the checker of the device-resident one.
+
+The reference binary (oracle/_ref/leandvb) is required by run_reference: where it is missing its callers FAIL.
+"""
+import ctypes as C
+import functools
+import os
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+from conftest import ROOT
+
+sys.path.insert(0, ROOT)
+
+REFBIN = os.path.join(ROOT, "oracle", "_ref", "leandvb")
+REF_U8 = ("--u8", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2")       # leandvb's arguments for the cu8 captures below
+
+
+@functools.lru_cache(maxsize=None)
+def capture(n_packets, seed, noise_std):
+    """A cu8 capture at 1.2 samples per symbol: (IQ items, the set of transmitted packets)."""
+    from leansdr_amd import synth_dvbs
+    iq, ts = synth_dvbs.capture_u8(n_packets=n_packets, sps_num=6, sps_den=5, seed=seed, noise_std=noise_std)
+    return np.ascontiguousarray(iq), {bytes(p) for p in np.asarray(ts, np.uint8).reshape(-1, 188)}
+
+
+def shifted(iq, f):
+    """The capture multiplied by exp(+j2π·f·n) and requantised to u8."""
+    a = iq.reshape(-1, 2).astype(np.float64) - 128
+    z = (a[:, 0] + 1j * a[:, 1]) * np.exp(2j * np.pi * f * np.arange(len(a)))
+    return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) + 128), 0, 255).astype(np.uint8).reshape(-1)
+
+
+def rotate_u8(iq, quarter_turns):
+    """(I, Q) → rotated by quarter_turns·90° on the cu8 grid (x ↦ 255 − x stands for the sign flip)."""
+    a = iq.reshape(-1, 2).copy()
+    for _ in range(quarter_turns % 4):
+        a = np.stack([255 - a[:, 1], a[:, 0]], axis=1)
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def six_variants(base, n, burst):
+    """[(name, IQ)] of an n-sample capture: as generated; rotated by 90, 180 and 270 degrees; `burst` samples of garbage in the middle (the
+    lock drops, then comes back); noise only (never locks)."""
+    rng = np.random.default_rng(5)
+    variants = [("as generated", base)]
+    for q in (1, 2, 3):
+        variants.append((f"rotated {90 * q} deg", rotate_u8(base, q)))
+    hit = base.copy()
+    hit[2 * (n // 2): 2 * (n // 2 + burst)] = rng.integers(100, 156, 2 * burst, dtype=np.uint8)
+    variants.append(("garbage burst in the middle", hit))
+    variants.append(("noise only (never locks)", rng.integers(96, 160, 2 * n, dtype=np.uint8).astype(np.uint8)))
+    return variants
+
+
+def run_reference(args, items):
+    """The reference binary's standard output for `items` on its standard input."""
+    assert os.path.exists(REFBIN) and os.access(REFBIN, os.X_OK), "oracle/_ref/leandvb is missing: build() makes it where the reference is present"
+    return subprocess.run([REFBIN] + list(args), input=items.tobytes(), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600).stdout
+
+
+@functools.lru_cache(maxsize=None)
+def reference_ts(args, n_packets, seed, noise_std, n_samples=None, shift=0.0):
+    """The reference binary's TS, under the arguments `args` (a tuple), for the first n_samples (None: all) of capture(n_packets, seed,
+    noise_std), shifted by `shift` cycles per sample first."""
+    iq = capture(n_packets, seed, noise_std)[0]
+    if shift:
+        iq = shifted(iq, shift)
+    return run_reference(args, iq if n_samples is None else iq[: 2 * n_samples])
+
+
+def references(keys):
+    """reference_ts(*key) of every key, eight processes at a time."""
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        return list(ex.map(lambda k: reference_ts(*k), keys))
+
+
+def packets(ts):
+    return [ts[i:i + 188] for i in range(0, len(ts), 188)]
+
+
+def check_against_reference(got, ref, sent, min_ref_packets, name, sent_from_first_compared):
+    """bench_c1.verify's rule with its numbers: behind the reference's acquisition the batch's TS is the reference's, up to 16 packets at the
+    end.  sent (None: not asked): every packet of the batch was transmitted — every one from the first compared one on with
+    sent_from_first_compared (under --hs --fastlock the reference's own first six packets are garbage), every one at all without.
+    Returns whether the whole TS is identical (recorded, not required)."""
+    import bench_c1
+    rpk, pk = packets(ref), packets(got)
+    # condition on the input: the reference decodes this capture
+    assert len(ref) % 188 == 0 and len(rpk) >= min_ref_packets, f"{name}: invalid input, the reference returns {len(rpk)} packets"
+    tail = rpk[bench_c1.SKIP_ACQ:]
+    assert len(tail) > 100 and tail[0] in pk, f"{name}: the reference's packet {bench_c1.SKIP_ACQ} is not in the batch's TS ({len(pk)} packets)"
+    i0 = pk.index(tail[0])
+    m = min(len(tail), len(pk) - i0)
+    assert pk[i0:i0 + m] == tail[:m], f"{name}: differs from the reference behind acquisition"
+    assert len(tail) - m <= 16, f"{name}: {len(tail) - m} of the reference's last packets not reached"
+    if sent is not None:
+        asked = pk[i0:] if sent_from_first_compared else pk
+        assert len(got) % 188 == 0 and all(p in sent for p in asked), f"{name}: a packet that was never transmitted"
+    same = got == ref
+    print(f"{name}: {len(pk)} packets, reference {len(rpk)}, compared {m}, first compared at {i0}, whole TS identical: {same}")
+    return same
+
+
+def decode_batch(ctx, iqs, n_samples, make, obj=None):
+    """One batch of the first n_samples of every capture on obj (None: on make()): (object, results, TS per capture)."""
+    bufs = [ctx.upload(iq[: 2 * n_samples]) for iq in iqs]
+    try:
+        if obj is None:
+            obj = make()
+        res, ts = obj.decode([b.ptr for b in bufs], n_samples)
+    finally:
+        for b in bufs:
+            b.free()
+    return obj, res, ts
+
+
+class HostTail:
+    """The FEC tail behind a front part of the caller's, driven by the HOST through the one-block-per-call C ABI (bench_c1.Worker.finish's
+    loop): the checker of the device-resident control flow.  The front part writes its bytes at d_bytes.at(bw) and adds their number to bw
+    (or hands all of them over as `data`); sync() runs mpeg_sync over what it has not taken yet; finish() runs deinterleaver → rs_decoder →
+    derandomizer and returns (front part's bytes, mpeg bytes, TS bytes, dict(npk, errs, locked))."""
+
+    def __init__(self, capi, ctx, byte_cap, fastlock=0, resync_period=None, data=None):
+        self.capi, self.ctx, self.byte_cap = capi, ctx, byte_cap
+        self.msync, self.derand = capi.MpegSync(ctx, fastlock=fastlock), capi.Derandomizer(ctx)
+        if resync_period is not None:
+            self.msync.set_resync_period(resync_period)
+        self.pk_cap = byte_cap // 204 + 64
+        self.d_bytes = ctx.alloc(byte_cap + 64) if data is None else ctx.upload(data)
+        self.d_mpeg = ctx.alloc(byte_cap + 64)
+        self.bw = 0 if data is None else len(data)
+        self.br = self.mw = 0
+
+    def sync(self, on_next_sync=None):
+        while True:
+            c, p, _, _, cns = self.msync.run_dev(self.d_bytes.at(self.br), self.bw - self.br, self.d_mpeg.at(self.mw), self.byte_cap - self.mw)
+            if cns and on_next_sync:
+                on_next_sync()
+            if not c and not p:
+                break
+            self.br += c; self.mw += p
+
+    def finish(self):
+        capi, ctx, lib, pk_cap = self.capi, self.ctx, self.capi.lib, self.pk_cap
+        d_rs, d_rts, d_ts = ctx.alloc(pk_cap * 204), ctx.alloc(pk_cap * 188), ctx.alloc(pk_cap * 188)
+        cons, prod = C.c_size_t(), C.c_size_t()
+        capi.check(lib.lsdr_deinterleaver_run(ctx.h, self.d_mpeg.ptr, self.mw, d_rs.ptr, pk_cap, C.byref(cons), C.byref(prod)))
+        npk, n_ts, errs = prod.value, 0, 0
+        if npk:
+            b, e = C.c_long(), C.c_long()
+            capi.check(lib.lsdr_rs_decoder_run(ctx.h, d_rs.ptr, npk, d_rts.ptr, C.byref(b), C.byref(e)))
+            errs = e.value
+            c2, p2 = C.c_size_t(), C.c_size_t()
+            capi.check(lib.lsdr_derandomizer_run(self.derand.h, d_rts.ptr, npk, d_ts.ptr, pk_cap, C.byref(c2), C.byref(p2)))
+            n_ts = p2.value
+        out = (ctx.download(self.d_bytes, np.uint8, self.bw), ctx.download(self.d_mpeg, np.uint8, self.mw), ctx.download(d_ts, np.uint8, n_ts * 188),
+               dict(npk=npk, errs=errs, locked=int(self.msync.locked)))
+        for d in (self.d_bytes, self.d_mpeg, d_rs, d_rts, d_ts):
+            d.free()
+        self.msync.close(); self.derand.close()
+        return out

@@ -11,19 +11,13 @@ The reference binary (oracle/_ref/leandvb) is required for 4: where it is missin
 """
 import ctypes as C
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
-from conftest import ROOT
+from batch_common import check_against_reference, run_reference
 
 pytestmark = pytest.mark.gpu
 
-sys.path.insert(0, ROOT)
-
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "leandvb")
 LSDR_E_ARG, LSDR_E_UNSUPPORTED = -2, -4
 DEC = 64 * 4096                                   # auto_notch::decimation lowered: 3 detect points in 1 Mi samples
 S8 = 0.00390625                                   # 2^-8
@@ -292,14 +286,11 @@ def test_true_16_bit_data_against_the_reference_binary(capi, ctx, n_packets, see
     bench_c1.verify's rule; the Viterbi cases also: every packet of the batch was transmitted (the default graph's first packets include
     some that never were — the reference's own acquisition)."""
     import bench_c1
-    assert os.path.exists(REFBIN) and os.access(REFBIN, os.X_OK), "oracle/_ref/leandvb is missing: build() makes it where the reference is present"
     s16, sent = _s16_capture(n_packets, seed, noise_std)
     n = len(s16) // 2
     args = ["--f32", "--float-scale", "0.00390625", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2"] + ([] if anf else ["--anf", "0"]) + (["--viterbi"] if viterbi else [])
-    ref = subprocess.run([REFBIN] + args, input=s16.astype(np.float32).tobytes(), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600).stdout
-    rpk = [ref[i:i + 188] for i in range(0, len(ref), 188)]
+    ref = run_reference(args, s16.astype(np.float32))
     name = f"{n_packets} packets seed {seed} noise {noise_std} {'--viterbi ' if viterbi else ''}anf {anf}"
-    assert len(ref) % 188 == 0 and len(rpk) >= min_ref, f"{name}: invalid input, the reference returns {len(rpk)} packets"
     cb = capi.CaptureBatch(ctx, 1, n, bench_c1.OMEGA, anf=anf, tile_len=4096, tile_warmup=512, viterbi=True if viterbi else None,
                            in_format=capi.IN_CS16, in_scale=S8)
     buf = ctx.upload(s16)
@@ -308,19 +299,8 @@ def test_true_16_bit_data_against_the_reference_binary(capi, ctx, n_packets, see
     finally:
         cb.close()
         buf.free()
-    got, r = ts[0], res[0]
-    pk = [got[i:i + 188] for i in range(0, len(got), 188)]
-    tail = rpk[bench_c1.SKIP_ACQ:]
-    same = got == ref
-    print(f"{name}: {len(pk)} packets, reference {len(rpk)}, whole TS identical: {same}")
-    assert tail[0] in pk, f"{name}: the reference's packet {bench_c1.SKIP_ACQ} is not in the batch's TS ({len(pk)} packets)"
-    i0 = pk.index(tail[0])
-    m = min(len(tail), len(pk) - i0)
-    assert pk[i0:i0 + m] == tail[:m], f"{name}: differs from the reference behind acquisition"
-    assert len(tail) - m <= 16, f"{name}: {len(tail) - m} of the reference's last packets not reached"
-    assert r["locked"] == 1 and r["seam_bad"] == 0, r
-    if viterbi:
-        assert len(got) % 188 == 0 and all(p in sent for p in pk), f"{name}: a packet that was never transmitted"
+    check_against_reference(ts[0], ref, sent if viterbi else None, min_ref, name, False)
+    assert res[0]["locked"] == 1 and res[0]["seam_bad"] == 0, res[0]
 
 
 # ---- 5 -----------------------------------------------------------------------------------------------------------------------------

@@ -11,16 +11,11 @@ shared launches with every data-dependent count on the device.
     C ABI produces when the host drives it (bench_c1.Worker's loop): deconvolved bytes, mpeg_sync output, TS — including captures that
     need next_sync() (rotated constellation), lose the lock in the middle (a burst of garbage) and never lock (noise only).
 """
-import ctypes as C
-import sys
-
 import numpy as np
 import pytest
-from conftest import ROOT
+from batch_common import HostTail, six_variants
 
 pytestmark = pytest.mark.gpu
-
-sys.path.insert(0, ROOT)
 
 
 def _job(capi, n_caps, msamples, groups, tile, warm, anf, seed0=4000):
@@ -53,52 +48,26 @@ def test_every_capture_decodes_to_the_reference_ts(capi, anf, tile):
 
 
 def _chain_reference(capi, ctx, words, nsym, byte_cap, window):
-    """The FEC tail driven by the HOST through the one-block-per-call C ABI (bench_c1.Worker.finish's loop): the checker of the
-    device-resident control flow.  `words`: the packed decisions on the device.  Returns (deconvolved bytes, mpeg bytes, TS bytes, stats)."""
-    lib = capi.lib
-    dec, msync, derand = capi.Deconv(ctx, capi.FEC12), capi.MpegSync(ctx), capi.Derandomizer(ctx)
-    pk_cap = byte_cap // 204 + 64
-    d_bytes, d_mpeg = ctx.alloc(byte_cap + 64), ctx.alloc(byte_cap + 64)
-    d_rs, d_rts, d_ts = ctx.alloc(pk_cap * 204), ctx.alloc(pk_cap * 188), ctx.alloc(pk_cap * 188)
-    pos = bw = br = mw = 0
-    next_sync = 0
+    """deconvol_sync in front of batch_common.HostTail, with mpeg_sync's next_sync() requests passed on.  `words`: the packed decisions on
+    the device.  Returns (deconvolved bytes, mpeg bytes, TS bytes, stats)."""
+    dec, t = capi.Deconv(ctx, capi.FEC12), HostTail(capi, ctx, byte_cap)
+    pos = calls = 0
+
+    def next_sync():
+        nonlocal calls
+        dec.next_sync()
+        calls += 1
+
     while True:
-        cap = byte_cap - bw if msync.locked else min(window, byte_cap - bw)
-        c, p = dec.run_dev_hs2(words, pos, nsym - pos, d_bytes.at(bw), cap)
+        cap = byte_cap - t.bw if t.msync.locked else min(window, byte_cap - t.bw)
+        c, p = dec.run_dev_hs2(words, pos, nsym - pos, t.d_bytes.at(t.bw), cap)
         if not p:
             break
-        pos += c; bw += p
-        while True:
-            c3, p3, _, _, cns = msync.run_dev(d_bytes.at(br), bw - br, d_mpeg.at(mw), byte_cap - mw)
-            if cns:
-                dec.next_sync(); next_sync += 1
-            if not c3 and not p3:
-                break
-            br += c3; mw += p3
-    cons, prod = C.c_size_t(), C.c_size_t()
-    capi.check(lib.lsdr_deinterleaver_run(ctx.h, d_mpeg.ptr, mw, d_rs.ptr, pk_cap, C.byref(cons), C.byref(prod)))
-    npk, n_ts, errs = prod.value, 0, 0
-    if npk:
-        b, e = C.c_long(), C.c_long()
-        capi.check(lib.lsdr_rs_decoder_run(ctx.h, d_rs.ptr, npk, d_rts.ptr, C.byref(b), C.byref(e)))
-        errs = e.value
-        c2, p2 = C.c_size_t(), C.c_size_t()
-        capi.check(lib.lsdr_derandomizer_run(derand.h, d_rts.ptr, npk, d_ts.ptr, pk_cap, C.byref(c2), C.byref(p2)))
-        n_ts = p2.value
-    out = (ctx.download(d_bytes, np.uint8, bw), ctx.download(d_mpeg, np.uint8, mw), ctx.download(d_ts, np.uint8, n_ts * 188),
-           dict(next_sync=next_sync, npk=npk, errs=errs, locked=int(msync.locked)))
-    for d in (d_bytes, d_mpeg, d_rs, d_rts, d_ts):
-        d.free()
-    dec.close(); msync.close(); derand.close()
-    return out
-
-
-def _rotate_u8(iq, quarter_turns):
-    """(I, Q) → rotated by quarter_turns·90° on the cu8 grid (x ↦ 255 − x stands for the sign flip)."""
-    a = iq.reshape(-1, 2).copy()
-    for _ in range(quarter_turns % 4):
-        a = np.stack([255 - a[:, 1], a[:, 0]], axis=1)
-    return np.ascontiguousarray(a).reshape(-1)
+        pos += c; t.bw += p
+        t.sync(next_sync)
+    want_bytes, want_mpeg, want_ts, st = t.finish()
+    dec.close()
+    return want_bytes, want_mpeg, want_ts, dict(st, next_sync=calls)
 
 
 @pytest.mark.parametrize("window", [0, 65536])
@@ -110,15 +79,7 @@ def test_device_resident_tail_equals_the_host_driven_block_chain(capi, ctx, wind
     gen.close()
     base = ctx.download(d0, np.uint8, 2 * n)
     d0.free()
-    rng = np.random.default_rng(5)
-    variants = []
-    variants.append(("as generated", base))
-    for q in (1, 2, 3):
-        variants.append((f"rotated {90 * q} deg (needs next_sync)", _rotate_u8(base, q)))
-    burst = base.copy()
-    burst[2 * (n // 2): 2 * (n // 2 + 300000)] = rng.integers(100, 156, 600000, dtype=np.uint8)      # the lock drops, then comes back
-    variants.append(("garbage burst in the middle", burst))
-    variants.append(("noise only (never locks)", rng.integers(96, 160, 2 * n, dtype=np.uint8).astype(np.uint8)))
+    variants = six_variants(base, n, 300000)                 # (the rotated ones need next_sync)
     short = base[: 2 * 70000].copy()
     bufs = [ctx.upload(v) for _, v in variants]
     cb = capi.CaptureBatch(ctx, len(variants), n, bench_c1.OMEGA, anf=0, tile_len=2048, tile_warmup=512, unlocked_window=window)

@@ -16,15 +16,12 @@ profiles/capture_batch_reports/deviation.txt).
 import ctypes as C
 import functools
 import os
-import sys
 
 import numpy as np
 import pytest
-from conftest import ROOT
+from batch_common import capture
 
 pytestmark = pytest.mark.gpu
-
-sys.path.insert(0, ROOT)
 
 LSDR_E_ARG = -2
 N = 1 << 20
@@ -43,10 +40,9 @@ def _tol(engine):
 def _captures(engine, anf, offset=0.0):
     """Two cu8 captures of N samples at the engine's noise; anf: with test_soft_symbols_against_the_oracle_chain's CW; offset: rotated by
     that many cycles per sample before re-quantising."""
-    from leansdr_amd import synth_dvbs
     out = []
     for k in range(2):
-        iq = synth_dvbs.capture_u8(600, sps_num=6, sps_den=5, seed=41 + k, noise_std=ENGINES[engine][1])[0][: 2 * N]
+        iq = capture(600, 41 + k, ENGINES[engine][1])[0][: 2 * N]
         if anf or offset:
             t = np.arange(N)
             x = (iq[0::2].astype(np.float64) - 128) + 1j * (iq[1::2].astype(np.float64) - 128)

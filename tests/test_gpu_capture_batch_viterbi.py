@@ -12,95 +12,35 @@ deinterleaver → rs_decoder → derandomizer), in shared launches.
 The reference binary (oracle/_ref/leandvb) is required: where it is missing these tests FAIL.
 """
 import ctypes as C
-import functools
-import os
-import subprocess
-import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
-from conftest import ROOT
+from batch_common import REF_U8, HostTail, capture, check_against_reference, decode_batch, references, six_variants
 
 pytestmark = pytest.mark.gpu
 
-sys.path.insert(0, ROOT)
-
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "leandvb")
-REF_ARGS = ["--u8", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2", "--viterbi"]
+REF_ARGS = REF_U8 + ("--viterbi",)
 WEAK = [(21, 12), (22, 15), (23, 18), (24, 20)]           # (seed, noise_std): the default graph returns 1446 / 1133 / 4 / 0 packets of 1500
-
-
-@functools.lru_cache(maxsize=None)
-def _capture(n_packets, seed, noise_std):
-    from leansdr_amd import synth_dvbs
-    iq, ts = synth_dvbs.capture_u8(n_packets=n_packets, sps_num=6, sps_den=5, seed=seed, noise_std=noise_std)
-    return np.ascontiguousarray(iq), {bytes(p) for p in np.asarray(ts, np.uint8).reshape(-1, 188)}
-
-
-@functools.lru_cache(maxsize=None)
-def _reference_ts(n_packets, seed, noise_std, n_samples, extra):
-    """The reference binary's TS for the first n_samples (None: all) of a capture; extra: more arguments, e.g. ("--anf", "0")."""
-    assert os.path.exists(REFBIN) and os.access(REFBIN, os.X_OK), "oracle/_ref/leandvb is missing: build() makes it where the reference is present"
-    iq, _ = _capture(n_packets, seed, noise_std)
-    if n_samples is not None:
-        iq = iq[: 2 * n_samples]
-    p = subprocess.run([REFBIN] + REF_ARGS + list(extra), input=iq.tobytes(), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600)
-    return p.stdout
-
-
-def _references(keys):
-    with ThreadPoolExecutor(max_workers=8) as ex:
-        return list(ex.map(lambda k: _reference_ts(*k), keys))
-
-
-def _packets(ts):
-    return [ts[i:i + 188] for i in range(0, len(ts), 188)]
-
-
-def _check_against_reference(got, ref, sent, min_ref_packets, name):
-    """bench_c1.verify's rule with its numbers.  Returns whether the whole TS is identical (recorded, not required)."""
-    import bench_c1
-    rpk, pk = _packets(ref), _packets(got)
-    # condition on the input: the reference decodes this capture
-    assert len(ref) % 188 == 0 and len(rpk) >= min_ref_packets, f"{name}: invalid input, the reference returns {len(rpk)} packets"
-    tail = rpk[bench_c1.SKIP_ACQ:]
-    assert len(tail) > 100 and tail[0] in pk, f"{name}: the reference's packet {bench_c1.SKIP_ACQ} is not in the batch's TS ({len(pk)} packets)"
-    i0 = pk.index(tail[0])
-    m = min(len(tail), len(pk) - i0)
-    assert pk[i0:i0 + m] == tail[:m], f"{name}: differs from the reference behind acquisition"
-    assert len(tail) - m <= 16, f"{name}: {len(tail) - m} of the reference's last packets not reached"
-    assert len(got) % 188 == 0 and all(p in sent for p in pk), f"{name}: a packet that was never transmitted"
-    same = got == ref
-    print(f"{name}: {len(pk)} packets, reference {len(rpk)}, compared {m}, first compared at {i0}, whole TS identical: {same}")
-    return same
 
 
 def _decode(capi, ctx, iqs, n_samples, anf, tile, cb=None):
     """One batch on a (new, unless given) Viterbi object: (object, results, TS per capture)."""
     import bench_c1
-    bufs = [ctx.upload(iq[: 2 * n_samples]) for iq in iqs]
-    try:
-        if cb is None:
-            cb = capi.CaptureBatch(ctx, len(iqs), n_samples, bench_c1.OMEGA, anf=anf, tile_len=tile, tile_warmup=512, viterbi=True)
-        res, ts = cb.decode([b.ptr for b in bufs], n_samples)
-    finally:
-        for b in bufs:
-            b.free()
-    return cb, res, ts
+    return decode_batch(ctx, iqs, n_samples, lambda: capi.CaptureBatch(ctx, len(iqs), n_samples, bench_c1.OMEGA, anf=anf, tile_len=tile, tile_warmup=512,
+                                                                       viterbi=True), cb)
 
 
 @pytest.mark.parametrize("tile", [4096, 2048])
 def test_weak_captures_decode_to_the_reference_ts(capi, ctx, tile):
     """B = 4, anf 0, noise 12 … 20: at 18 and 20 the default engine returns nothing."""
-    caps = [_capture(1500, s, n) for s, n in WEAK]
+    caps = [capture(1500, s, n) for s, n in WEAK]
     n = len(caps[0][0]) // 2
     assert n == 2937623 and all(len(c[0]) == 2 * n for c in caps)
-    refs = _references([(1500, s, nz, None, ("--anf", "0")) for s, nz in WEAK])
+    refs = references([(REF_ARGS + ("--anf", "0"), 1500, s, nz) for s, nz in WEAK])
     cb, res, ts = _decode(capi, ctx, [c[0] for c in caps], n, 0, tile)
     try:
         for i, (s, nz) in enumerate(WEAK):
-            _check_against_reference(ts[i], refs[i], caps[i][1], 1400, f"seed {s} noise {nz} tile {tile}")
+            check_against_reference(ts[i], refs[i], caps[i][1], 1400, f"seed {s} noise {nz} tile {tile}", False)
             r = res[i]
             assert r["locked"] == 1 and r["seam_bad"] == 0 and r["next_sync_calls"] == 0, r
             st = cb.viterbi_stats(i)
@@ -114,19 +54,19 @@ def test_weak_captures_decode_to_the_reference_ts(capi, ctx, tile):
 
 def test_across_a_detect_point_with_the_notch(capi, ctx):
     """anf = 1 (leandvb's default), 5.9 M samples: the first detect point is at sample 4 190 208.  Then a short run on the same object."""
-    iq, sent = _capture(3000, 31, 18)
+    iq, sent = capture(3000, 31, 18)
     n = len(iq) // 2
     assert n == 5875223
-    iq23, sent23 = _capture(1500, 23, 18)
-    ref, ref_short = _references([(3000, 31, 18, None, ()), (1500, 23, 18, 1000000, ())])
+    iq23, sent23 = capture(1500, 23, 18)
+    ref, ref_short = references([(REF_ARGS, 3000, 31, 18), (REF_ARGS, 1500, 23, 18, 1000000)])
     cb, res, ts = _decode(capi, ctx, [iq, iq], n, 1, 4096)
     try:
-        _check_against_reference(ts[0], ref, sent, 2900, "seed 31 noise 18 anf 1")
+        check_against_reference(ts[0], ref, sent, 2900, "seed 31 noise 18 anf 1", False)
         assert ts[0] == ts[1]
         assert all(r["locked"] == 1 and r["seam_bad"] == 0 and r["next_sync_calls"] == 0 for r in res), res
         assert len(cb.bins(0)) == 1
         _, res2, ts2 = _decode(capi, ctx, [iq23, iq23], 1000000, 1, 4096, cb=cb)
-        _check_against_reference(ts2[0], ref_short, sent23, 400, "seed 23 noise 18, 1 000 000 samples, second run")
+        check_against_reference(ts2[0], ref_short, sent23, 400, "seed 23 noise 18, 1 000 000 samples, second run", False)
         assert ts2[0] == ts2[1]
         assert all(r["samples"] == (1000000 // 4096 * 4096 - 1) // 128 * 128 for r in res2), res2
     finally:
@@ -180,50 +120,22 @@ def test_soft_symbols_against_the_oracle_chain(capi, ctx, oracle, anf, tile, cw_
             b.free()
 
 
-def _rotate_u8(iq, quarter_turns):
-    a = iq.reshape(-1, 2).copy()
-    for _ in range(quarter_turns % 4):
-        a = np.stack([255 - a[:, 1], a[:, 0]], axis=1)
-    return np.ascontiguousarray(a).reshape(-1)
-
-
 def _stage_reference(capi, ctx, soft_ptr, nsym):
-    """What the one-block-per-call C ABI makes of the soft symbols at soft_ptr when the host drives it: a fresh lsdr_viterbi_run, then
-    mpeg_sync (nobody to call next_sync() on) → deinterleaver → rs_decoder → derandomizer.  Returns (bytes, mpeg bytes, TS, stats)."""
-    lib = capi.lib
+    """What the one-block-per-call C ABI makes of the soft symbols at soft_ptr when the host drives it: a fresh lsdr_viterbi_run in front of
+    batch_common.HostTail (nobody to call next_sync() on).  Returns (bytes, mpeg bytes, TS, stats)."""
     byte_cap = nsym // 4 + 65536
-    pk_cap = byte_cap // 204 + 64
-    vit, msync, derand = capi.Viterbi(ctx, capi.QPSK, capi.FEC12), capi.MpegSync(ctx), capi.Derandomizer(ctx)
-    d_bytes, d_mpeg = ctx.alloc(byte_cap + 64), ctx.alloc(byte_cap + 64)
-    d_rs, d_rts, d_ts = ctx.alloc(pk_cap * 204), ctx.alloc(pk_cap * 188), ctx.alloc(pk_cap * 188)
-    done = bw = 0
+    vit, t = capi.Viterbi(ctx, capi.QPSK, capi.FEC12), HostTail(capi, ctx, byte_cap)
+    done = 0
     while True:                                   # (one call takes every chunk that fits; the next one finds nothing)
-        c, p = vit.run_dev(C.c_void_p(soft_ptr + 4 * done), nsym - done, d_bytes.at(bw), byte_cap - bw)
+        c, p = vit.run_dev(C.c_void_p(soft_ptr + 4 * done), nsym - done, t.d_bytes.at(t.bw), byte_cap - t.bw)
         if not c:
             break
-        done += c; bw += p
-    br = mw = 0
-    while True:
-        c3, p3, _, _, _ = msync.run_dev(d_bytes.at(br), bw - br, d_mpeg.at(mw), byte_cap - mw)
-        if not c3 and not p3:
-            break
-        br += c3; mw += p3
-    cons, prod = C.c_size_t(), C.c_size_t()
-    capi.check(lib.lsdr_deinterleaver_run(ctx.h, d_mpeg.ptr, mw, d_rs.ptr, pk_cap, C.byref(cons), C.byref(prod)))
-    npk, n_ts, errs = prod.value, 0, 0
-    if npk:
-        b, e = C.c_long(), C.c_long()
-        capi.check(lib.lsdr_rs_decoder_run(ctx.h, d_rs.ptr, npk, d_rts.ptr, C.byref(b), C.byref(e)))
-        errs = e.value
-        c2, p2 = C.c_size_t(), C.c_size_t()
-        capi.check(lib.lsdr_derandomizer_run(derand.h, d_rts.ptr, npk, d_ts.ptr, pk_cap, C.byref(c2), C.byref(p2)))
-        n_ts = p2.value
-    out = (ctx.download(d_bytes, np.uint8, bw), ctx.download(d_mpeg, np.uint8, mw), ctx.download(d_ts, np.uint8, n_ts * 188),
-           dict(npk=npk, errs=errs, locked=int(msync.locked), sync=int(vit.current_sync)))
-    for d in (d_bytes, d_mpeg, d_rs, d_rts, d_ts):
-        d.free()
-    vit.close(); msync.close(); derand.close()
-    return out
+        done += c; t.bw += p
+    t.sync()
+    want_bytes, want_mpeg, want_ts, st = t.finish()
+    st["sync"] = int(vit.current_sync)
+    vit.close()
+    return want_bytes, want_mpeg, want_ts, st
 
 
 def _assert_stages_exact(capi, ctx, cb, res, ts, names):
@@ -250,14 +162,7 @@ def test_viterbi_stage_and_tail_are_exact_on_the_objects_own_soft_symbols(capi, 
     gen.close()
     base = ctx.download(d0, np.uint8, 2 * n)
     d0.free()
-    rng = np.random.default_rng(5)
-    variants = [("as generated", base)]
-    for q in (1, 2, 3):
-        variants.append((f"rotated {90 * q} deg", _rotate_u8(base, q)))
-    burst = base.copy()
-    burst[2 * (n // 2): 2 * (n // 2 + 300000)] = rng.integers(100, 156, 600000, dtype=np.uint8)
-    variants.append(("garbage burst in the middle", burst))
-    variants.append(("noise only (never locks)", rng.integers(96, 160, 2 * n, dtype=np.uint8).astype(np.uint8)))
+    variants = six_variants(base, n, 300000)
     names = [v[0] for v in variants]
     bufs = [ctx.upload(v) for _, v in variants]
     cb = capi.CaptureBatch(ctx, len(variants), n, bench_c1.OMEGA, anf=0, tile_len=2048, tile_warmup=512, viterbi=True)
@@ -285,7 +190,7 @@ def test_viterbi_stage_and_tail_are_exact_on_the_objects_own_soft_symbols(capi, 
 
 
 def test_neighbours_do_not_matter(capi, ctx):
-    caps = [_capture(1500, s, n)[0] for s, n in WEAK]
+    caps = [capture(1500, s, n)[0] for s, n in WEAK]
     n = len(caps[0]) // 2
     cb4, res4, ts4 = _decode(capi, ctx, caps, n, 0, 4096)
     st4 = cb4.viterbi_stats(2)
@@ -308,7 +213,7 @@ def test_neighbours_do_not_matter(capi, ctx):
 def test_two_partitions_give_the_same_ts(capi, ctx):
     """aux_cus: the tiles on one compute-unit partition, everything else — Viterbi stage and tail included — on the other."""
     import bench_c1
-    iq = _capture(1500, 23, 18)[0]
+    iq = capture(1500, 23, 18)[0]
     n = len(iq) // 2
     cb0, res0, ts0 = _decode(capi, ctx, [iq, iq], n, 0, 4096)
     cb0.close()

@@ -15,98 +15,29 @@ default 1 024-sample tile, 1 912 deconvolver chunks, 59 resyncs at P = 32.
 The reference binary (oracle/_ref/leandvb) is required: where it is missing these tests FAIL.
 """
 import functools
-import os
-import subprocess
-import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
-from conftest import ROOT
+from batch_common import REF_U8, HostTail, capture, check_against_reference, decode_batch, references, shifted, six_variants
 
 pytestmark = pytest.mark.gpu
 
-sys.path.insert(0, ROOT)
-
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "leandvb")
-REF_ARGS = ["--u8", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2", "--hs"]
+REF_ARGS = REF_U8 + ("--hs",)
 FS = 2400e3
 OMEGA = 1.2
 CAPS = [(21, 6.0), (22, 9.0), (23, 12.0), (24, 7.5)]      # (seed, noise_std)
 N_SAMPLES = 1175063
 
 
-@functools.lru_cache(maxsize=None)
 def _capture(seed, noise_std):
-    from leansdr_amd import synth_dvbs
-    iq, ts = synth_dvbs.capture_u8(n_packets=600, sps_num=6, sps_den=5, seed=seed, noise_std=noise_std)
-    iq = np.ascontiguousarray(iq)
+    iq, sent = capture(600, seed, noise_std)
     assert len(iq) == 2 * N_SAMPLES
-    return iq, {bytes(p) for p in np.asarray(ts, np.uint8).reshape(-1, 188)}
-
-
-def _shifted(iq, f):
-    """The capture multiplied by exp(+j2π·f·n) and requantised to u8."""
-    a = iq.reshape(-1, 2).astype(np.float64) - 128
-    z = (a[:, 0] + 1j * a[:, 1]) * np.exp(2j * np.pi * f * np.arange(len(a)))
-    return np.clip(np.rint(np.stack([z.real, z.imag], axis=1) + 128), 0, 255).astype(np.uint8).reshape(-1)
-
-
-def _rotate_u8(iq, quarter_turns):
-    a = iq.reshape(-1, 2).copy()
-    for _ in range(quarter_turns % 4):
-        a = np.stack([255 - a[:, 1], a[:, 0]], axis=1)
-    return np.ascontiguousarray(a).reshape(-1)
-
-
-def _run_reference(iq, extra):
-    assert os.path.exists(REFBIN) and os.access(REFBIN, os.X_OK), "oracle/_ref/leandvb is missing: build() makes it where the reference is present"
-    p = subprocess.run([REFBIN] + REF_ARGS + list(extra), input=iq.tobytes(), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600)
-    return p.stdout
-
-
-@functools.lru_cache(maxsize=None)
-def _reference_ts(seed, noise_std, shift, extra):
-    iq = _capture(seed, noise_std)[0]
-    return _run_reference(_shifted(iq, shift) if shift else iq, extra)
-
-
-def _references(keys):
-    with ThreadPoolExecutor(max_workers=8) as ex:
-        return list(ex.map(lambda k: _reference_ts(*k), keys))
-
-
-def _packets(ts):
-    return [ts[i:i + 188] for i in range(0, len(ts), 188)]
-
-
-def _check_against_reference(got, ref, sent, min_ref_packets, name):
-    """The rule of test_gpu_capture_batch_viterbi._check_against_reference, except that "a transmitted packet" is asked of the batch's
-    packets from the first compared one on: under --fastlock the reference's own first six packets are garbage."""
-    import bench_c1
-    rpk, pk = _packets(ref), _packets(got)
-    assert len(ref) % 188 == 0 and len(rpk) >= min_ref_packets, f"{name}: invalid input, the reference returns {len(rpk)} packets"
-    tail = rpk[bench_c1.SKIP_ACQ:]
-    assert len(tail) > 100 and tail[0] in pk, f"{name}: the reference's packet {bench_c1.SKIP_ACQ} is not in the batch's TS ({len(pk)} packets)"
-    i0 = pk.index(tail[0])
-    m = min(len(tail), len(pk) - i0)
-    assert pk[i0:i0 + m] == tail[:m], f"{name}: differs from the reference behind acquisition"
-    assert len(tail) - m <= 16, f"{name}: {len(tail) - m} of the reference's last packets not reached"
-    assert len(got) % 188 == 0 and all(p in sent for p in pk[i0:]), f"{name}: a packet that was never transmitted"
-    print(f"{name}: {len(pk)} packets, reference {len(rpk)}, compared {m}, first compared at {i0}, whole TS identical: {got == ref}")
+    return iq, sent
 
 
 def _decode(capi, ctx, iqs, n_samples, hb=None, **kw):
     """One batch on a (new, unless given) object: (object, results, TS per capture)."""
-    bufs = [ctx.upload(iq[: 2 * n_samples]) for iq in iqs]
-    try:
-        if hb is None:
-            hb = capi.HsBatch(ctx, len(iqs), n_samples, OMEGA, **kw)
-        res, ts = hb.decode([b.ptr for b in bufs], n_samples)
-    finally:
-        for b in bufs:
-            b.free()
-    return hb, res, ts
+    return decode_batch(ctx, iqs, n_samples, lambda: capi.HsBatch(ctx, len(iqs), n_samples, OMEGA, **kw), hb)
 
 
 @functools.lru_cache(maxsize=None)
@@ -125,10 +56,10 @@ def _batch_of_four(capi, ctx, fastlock, tile_len, tile_warmup):
 @pytest.mark.parametrize("fastlock", [0, 1])
 def test_captures_decode_to_the_reference_ts(capi, ctx, fastlock, tile_len, tile_warmup):
     extra = ("--fastlock",) if fastlock else ()
-    refs = _references([(s, nz, 0.0, extra) for s, nz in CAPS])
+    refs = references([(REF_ARGS + extra, 600, s, nz) for s, nz in CAPS])
     res, ts, _ = _batch_of_four(capi, ctx, fastlock, tile_len, tile_warmup)
     for i, (s, nz) in enumerate(CAPS):
-        _check_against_reference(ts[i], refs[i], _capture(s, nz)[1], 540, f"seed {s} noise {nz} fastlock {fastlock} tile {tile_len}")
+        check_against_reference(ts[i], refs[i], _capture(s, nz)[1], 540, f"seed {s} noise {nz} fastlock {fastlock} tile {tile_len}", True)
         r = res[i]
         assert r["locked"] == 1 and r["seam_bad"] == 0 and r["next_sync_calls"] == 0, r
         assert r["samples"] == (N_SAMPLES - 1) // 128 * 128 and r["ts_packets"] * 188 == len(ts[i])
@@ -158,25 +89,16 @@ def test_symbols_against_the_oracle(capi, ctx, oracle):
 
 
 def _stage_reference(capi, ctx, sym, P):
-    """What the one-block-per-call C ABI makes of hard symbols when the host drives it: a fresh dvb_deconvol_sync, mpeg_sync(fastlock = 1,
-    resync_period P), deinterleaver, rs_decoder, derandomizer."""
+    """What the one-block-per-call C ABI makes of hard symbols when the host drives it: a fresh dvb_deconvol_sync in front of
+    batch_common.HostTail with mpeg_sync(fastlock = 1, resync_period P)."""
     d = capi.HsDeconv(ctx, P)
     by = d.run_stream(sym)
     alignment = int(d.locked)
     d.close()
-    m = capi.MpegSync(ctx, fastlock=1)
-    m.set_resync_period(P)
-    mb, _ = m.run_stream(by)
-    locked = int(m.locked)
-    m.close()
-    pk = capi.deinterleaver(ctx, mb)[0] if len(mb) else []
-    npk, errs, ts = len(pk), 0, b""
-    if npk:
-        rts, _, errs = capi.rs_decoder(ctx, pk)
-        dr = capi.Derandomizer(ctx)
-        ts = dr.run(rts).tobytes()
-        dr.close()
-    return by, mb, ts, dict(npk=npk, errs=errs, locked=locked, alignment=alignment)
+    t = HostTail(capi, ctx, len(by) + 4096, fastlock=1, resync_period=P, data=by)
+    t.sync()
+    want_bytes, want_mpeg, want_ts, st = t.finish()
+    return want_bytes, want_mpeg, want_ts.tobytes(), dict(st, alignment=alignment)
 
 
 def _assert_stages_exact(capi, ctx, hb, res, ts, names, P):
@@ -201,15 +123,8 @@ def test_deconvolver_and_tail_are_exact_on_the_objects_own_symbols(capi, ctx, fa
     P = 1 if fastlock else 32
     base = _capture(23, 12.0)[0]
     n = N_SAMPLES
-    rng = np.random.default_rng(5)
-    variants = [("as generated", base)]
-    for q in (1, 2, 3):
-        variants.append((f"rotated {90 * q} deg", _rotate_u8(base, q)))
-    variants.append(("I/Q swapped", np.ascontiguousarray(base.reshape(-1, 2)[:, ::-1]).reshape(-1)))
-    burst = base.copy()
-    burst[2 * (n // 2): 2 * (n // 2 + 100000)] = rng.integers(100, 156, 200000, dtype=np.uint8)
-    variants.append(("garbage burst in the middle", burst))
-    variants.append(("noise only (never locks)", rng.integers(96, 160, 2 * n, dtype=np.uint8).astype(np.uint8)))
+    variants = six_variants(base, n, 100000)
+    variants.insert(4, ("I/Q swapped", np.ascontiguousarray(base.reshape(-1, 2)[:, ::-1]).reshape(-1)))
     names = [v[0] for v in variants]
     hb, res, ts = _decode(capi, ctx, [v for _, v in variants], n, fastlock=fastlock)
     try:
@@ -273,13 +188,13 @@ def test_carrier_offset(capi, ctx, oracle):
     iq, sent = _capture(23, 12.0)
     fa, fb = 2e-4, 1e-3
     # the sign of `freq` is lsdr_fastqpsk_create's: the exact receiver ends at +f for a capture multiplied by exp(+j2π·f·n)
-    o = oracle.fast_qpsk(_shifted(iq, fb)[: 2 * 400000], OMEGA)
+    o = oracle.fast_qpsk(shifted(iq, fb)[: 2 * 400000], OMEGA)
     assert abs(o["freqw"] / 65536.0 - fb) < 1e-4, o["freqw"]
-    refs = _references([(23, 12.0, fa, ()), (23, 12.0, fb, ("--tune", str(fb * FS)))])
+    refs = references([(REF_ARGS, 600, 23, 12.0, None, fa), (REF_ARGS + ("--tune", str(fb * FS)), 600, 23, 12.0, None, fb)])
     for name, f, freq, ref in (("offset 2e-4 untuned", fa, 0.0, refs[0]), ("offset 1e-3 tuned", fb, fb, refs[1])):
-        hb, res, ts = _decode(capi, ctx, [_shifted(iq, f)], N_SAMPLES, freq=freq)
+        hb, res, ts = _decode(capi, ctx, [shifted(iq, f)], N_SAMPLES, freq=freq)
         hb.close()
-        _check_against_reference(ts[0], ref, sent, 540, name)
+        check_against_reference(ts[0], ref, sent, 540, name, True)
         assert res[0]["locked"] == 1 and res[0]["seam_bad"] == 0, res[0]
 
 

@@ -9,8 +9,8 @@ around it (lsdr_capture_batch_tile_time) and run_async + wait on the host clock.
 object's results and TS (checked before the clock starts); each capture's last SS / MER / FREQ is printed.
 
 --parent-root DIR: a built checkout of the parent commit.  The same measurement (reports off: all it has) is then run on it too, in
-processes that alternate with this checkout's — `rounds` processes each — and the result holds both tile times and the parent's
-run-to-run spread: an object without reports launches the kernels it launched there.
+processes that alternate with this checkout's — `rounds` processes each — and the result holds both tile times, both run_async + wait
+times and the parent's run-to-run spread: an object without reports launches the kernels it launched there.
 
 Writes one JSON line to --out (default profiles/capture_batch_reports/bench.json) and to stdout."""
 import argparse
@@ -132,7 +132,9 @@ def main():
                              tile_kernel_ms_parent=dict(per_process=p, median=round(statistics.median(p), 4)),
                              parent_run_to_run_spread_ms=round(max(p) - min(p), 4),
                              parent_round_to_round_spread_ms=round(max(max(r[e]["tile_kernel_ms_off"]["rounds"]) - min(r[e]["tile_kernel_ms_off"]["rounds"]) for r in parent), 4),
-                             difference_ms=round(statistics.median(t) - statistics.median(p), 4)))
+                             difference_ms=round(statistics.median(t) - statistics.median(p), 4),
+                             seconds_per_batch_reports_off=[r[e]["seconds_per_batch_off"] for r in this],
+                             seconds_per_batch_parent=[r[e]["seconds_per_batch_off"] for r in parent]))
         result["against_the_parent_commit"] = cmp_
     line = json.dumps(result)
     print(line)
