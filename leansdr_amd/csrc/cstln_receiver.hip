@@ -1495,7 +1495,7 @@ static int rx_pull_state(lsdr_rx *r) {   // refresh the host mirror after queued
 // slot) without waiting; rx_tiled_wait retires the oldest queued run.
 // One queued run in three steps, so that several receivers can share the launches (lsdr_rx_run_multi_async):
 //   rx_tiled_plan    sizes, scratch, the argument record (no launch); chunks == 0: nothing to do
-//   rx_tiled_launch  the run's kernels on the receiver's stream (or: the multi-capture launches over several plans)
+//   rx_tiled_launch  the kernels of one run, or of the runs of several receivers planned alike, on the receivers' stream
 //   rx_tiled_commit  ring slot, completion event, host-side bookkeeping
 struct rx_plan {
   rx_tiled_args a;
@@ -1506,6 +1506,40 @@ struct rx_plan {
   bool want_meas, want_cstln, use_lds, hard;
   int slot;
 };
+
+// Tuning and test hooks of the tiled receiver, read once per process.
+struct rx_hooks {
+  bool no_lds_set; int no_lds;     // LSDR_RX_NO_LDS: set at all: no cu8 span cut; 1: direct loads (A/B measurements); 2: direct loads for cf32 input only
+  unsigned long long lds_span;     // LSDR_RX_LDS_SPAN: test hook, bytes the staged cu8 tiles' 32-bit offsets reach
+  int lanes;                       // LSDR_RX_LANES: tiles per wavefront (0: the default)
+  bool prio;                       // LSDR_RX_PRIO
+  unsigned dbg; bool skip;         // measure build only: LSDR_RX_DBG timing-only tiles, LSDR_RX_SKIP no receiver kernels at all (results are garbage)
+};
+static const rx_hooks &rx_env() {
+  static const rx_hooks h = [] {
+    rx_hooks v;
+    const char *e = getenv("LSDR_RX_NO_LDS");
+    v.no_lds_set = e != nullptr; v.no_lds = e ? atoi(e) : 0;
+    v.lds_span = (e = getenv("LSDR_RX_LDS_SPAN")) ? strtoull(e, nullptr, 0) : 0xfff00000ull;
+    v.lanes = (e = getenv("LSDR_RX_LANES")) ? atoi(e) : 0;
+    v.prio = (e = getenv("LSDR_RX_PRIO")) && atoi(e);
+    v.dbg = (e = LSDR_MEASURE_ENV("LSDR_RX_DBG")) ? (unsigned)atoi(e) & 3u : 0u;
+    v.skip = LSDR_MEASURE_ENV("LSDR_RX_SKIP") != nullptr;
+    return v;
+  }();
+  return h;
+}
+
+// Scratch that only grows: a buffer short of `need` elements is freed and allocated anew (its contents are not kept).  Runs queued
+// earlier may still use the old buffer: the caller synchronises the stream before the first growth.
+template <typename T>
+static int rx_grow(T **buf, size_t *cap, size_t need) {
+  if (*cap >= need) return LSDR_OK;
+  (void)hipFree(*buf); *buf = nullptr; *cap = 0;
+  LSDR_HIP(hipMalloc((void **)buf, need * sizeof(T)));
+  *cap = need;
+  return LSDR_OK;
+}
 
 static int rx_tiled_plan(lsdr_rx *r, unsigned share, const void *in, size_t n_in, lsdr_softsymbol *out, size_t cap_out,
                          bool want_meas, size_t meas_cap, size_t cstln_cap, rx_plan *P) {
@@ -1528,17 +1562,19 @@ static int rx_tiled_plan(lsdr_rx *r, unsigned share, const void *in, size_t n_in
   if ((size_t)(sym_per_chunk + 1) * chunks > cap_out) chunks = cap_out / (sym_per_chunk + 1);
   const bool want_cstln = cstln_cap > 0;
   if (want_cstln && chunks > cstln_cap) chunks = cstln_cap;     // one sampled point per chunk at most (sdr.h:785-788 gate)
-  {
+  // nearest / linear sampler: the tiles' samples are staged through LDS (see rx_tile_tol) — cu8 always; cf32 when all 64 rows of a
+  // stage belong to tiles of the wavefront and the launch is small enough (≤ 1024 wavefronts) that its 9 KiB per wavefront do not
+  // decide how many are resident (decided below, where the launch geometry is known): C3's 4 Gi-sample batches are 8.7 K wavefronts,
+  // and next to fir_filter's 114 KiB per CU only four of them fit a CU — direct loads (no LDS) ran that chain 12 % faster.
+  const rx_hooks &H = rx_env();
+  const bool cu8 = r->cfg.in_format == LSDR_IN_CU8;
+  bool use_lds = r->cfg.sampler != LSDR_SAMP_FIR && (cu8 ? H.no_lds != 1 && r->omega <= 8.f : H.no_lds == 0);
+  if (use_lds && cu8 && !H.no_lds_set) {
     // LDS-staged cu8 tiles address their samples through a buffer resource with 32-bit byte offsets (rows beyond 0xfff00000 are
     // pointed past the end and read zeros): a run is cut to what those offsets reach — `consumed` reports the partial run and the
-    // caller comes back with the rest, as with any other limit.  (LSDR_RX_LDS_SPAN: test hook, bytes.)
-    static const bool no_lds0 = getenv("LSDR_RX_NO_LDS") != nullptr;
-    static const unsigned long long span = getenv("LSDR_RX_LDS_SPAN") ? strtoull(getenv("LSDR_RX_LDS_SPAN"), nullptr, 0) : 0xfff00000ull;
-    const bool lds_tiles = r->cfg.in_format == LSDR_IN_CU8 && r->cfg.sampler != LSDR_SAMP_FIR && !no_lds0 && r->omega <= 8.f;
-    if (lds_tiles) {
-      const unsigned long long max_samples = (span - 64) / 2;
-      if ((unsigned long long)chunks * kChunk + (unsigned)ra > max_samples) chunks = (size_t)((max_samples - (unsigned)ra) / kChunk);
-    }
+    // caller comes back with the rest, as with any other limit.
+    const unsigned long long max_samples = (H.lds_span - 64) / 2;
+    if ((unsigned long long)chunks * kChunk + (unsigned)ra > max_samples) chunks = (size_t)((max_samples - (unsigned)ra) / kChunk);
   }
   const int slot = (r->ring_head + r->ring_count) % lsdr_rx::kRing;
   P->slot = slot; P->chunks = chunks; P->want_meas = want_meas; P->want_cstln = want_cstln;
@@ -1552,8 +1588,16 @@ static int rx_tiled_plan(lsdr_rx *r, unsigned share, const void *in, size_t n_in
   const bool hard = r->cfg.out_format == LSDR_SYM_HARD2;
   const unsigned hstride = stage_stride / 16 + 2;          // words per tile
   const unsigned long long hpitch = ((unsigned long long)n_tiles + 63) & ~63ull;   // transposed staging: word w of tile j at [w·hpitch + j]
-  if (r->tiles_cap < n_tiles || (!hard && (r->stage_cap < (size_t)n_tiles * stage_stride || r->wstage_cap < (size_t)n_tiles * sym_per_chunk)) ||
-      (hard && r->hstage_cap < (size_t)hpitch * hstride)) {
+  const unsigned long long md = r->cfg.meas_decimation;
+  const unsigned long long meas_base = r->st.meas_count;   // kept current on the host even while `st` is stale
+  const size_t nm = (size_t)((meas_base + chunks * kChunk) / md - meas_base / md);
+  P->nm = nm; P->meas_base = meas_base; P->md = md;
+  if (want_meas && nm > meas_cap) { lsdr_set_error("cstln_receiver(tiled): measurement buffers too small"); return LSDR_E_ARG; }
+  // scratch: a kind of output the receiver does not produce needs none
+  const size_t need_hstage = hard ? (size_t)hpitch * hstride : 0, need_stage = hard ? 0 : (size_t)n_tiles * stage_stride,
+               need_wstage = hard ? 0 : (size_t)n_tiles * sym_per_chunk, need_meas = want_meas ? nm + 1 : 0, need_cstln = want_cstln ? chunks : 0;
+  if (r->tiles_cap < n_tiles || r->hstage_cap < need_hstage || r->stage_cap < need_stage || r->wstage_cap < need_wstage ||
+      r->meas_cap < need_meas || r->cstln_cap < need_cstln) {
     // scratch grows: queued runs may still be using the old buffers
     LSDR_HIP(hipStreamSynchronize(c->stream));
   }
@@ -1569,38 +1613,11 @@ static int rx_tiled_plan(lsdr_rx *r, unsigned share, const void *in, size_t n_in
     if (hard) LSDR_HIP(hipMalloc((void **)&r->d_hinfo, n_tiles * sizeof(rx_tile_info_h)));
     r->tiles_cap = n_tiles;
   }
-  if (hard && r->hstage_cap < (size_t)hpitch * hstride) {
-    (void)hipFree(r->d_hstage);
-    LSDR_HIP(hipMalloc((void **)&r->d_hstage, (size_t)hpitch * hstride * sizeof(unsigned)));
-    r->hstage_cap = (size_t)hpitch * hstride;
-  }
-  if (!hard && r->stage_cap < (size_t)n_tiles * stage_stride) {
-    (void)hipFree(r->d_stage);
-    LSDR_HIP(hipMalloc((void **)&r->d_stage, (size_t)n_tiles * stage_stride * sizeof(lsdr_softsymbol)));
-    r->stage_cap = (size_t)n_tiles * stage_stride;
-  }
-  if (!hard && r->wstage_cap < (size_t)n_tiles * sym_per_chunk) {
-    (void)hipFree(r->d_wstage);
-    LSDR_HIP(hipMalloc((void **)&r->d_wstage, (size_t)n_tiles * sym_per_chunk * sizeof(lsdr_softsymbol)));
-    r->wstage_cap = (size_t)n_tiles * sym_per_chunk;
-  }
-  const unsigned long long md = r->cfg.meas_decimation;
-  const unsigned long long meas_base = r->st.meas_count;   // kept current on the host even while `st` is stale
-  const size_t nm = (size_t)((meas_base + chunks * kChunk) / md - meas_base / md);
-  P->nm = nm; P->meas_base = meas_base; P->md = md;
-  if (want_meas && nm > meas_cap) { lsdr_set_error("cstln_receiver(tiled): measurement buffers too small"); return LSDR_E_ARG; }
-  if (want_meas && r->meas_cap < nm + 1) {
-    LSDR_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(r->d_meas);
-    LSDR_HIP(hipMalloc((void **)&r->d_meas, (nm + 1) * sizeof(rx_meas)));
-    r->meas_cap = nm + 1;
-  }
-  if (want_cstln && r->cstln_cap < chunks) {
-    LSDR_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(r->d_cstln);
-    LSDR_HIP(hipMalloc((void **)&r->d_cstln, chunks * sizeof(float2)));
-    r->cstln_cap = chunks;
-  }
+  LSDR_TRY(rx_grow(&r->d_hstage, &r->hstage_cap, need_hstage));
+  LSDR_TRY(rx_grow(&r->d_stage, &r->stage_cap, need_stage));
+  LSDR_TRY(rx_grow(&r->d_wstage, &r->wstage_cap, need_wstage));
+  LSDR_TRY(rx_grow(&r->d_meas, &r->meas_cap, need_meas));
+  LSDR_TRY(rx_grow(&r->d_cstln, &r->cstln_cap, need_cstln));
   int rc = rx_push_state(r);
   if (rc) return rc;
 
@@ -1627,30 +1644,16 @@ static int rx_tiled_plan(lsdr_rx *r, unsigned share, const void *in, size_t n_in
   // 64 → 302 GS/s whole-job).  With more than ≈ 12 K tiles in a launch (short tiles, or the captures of a GPU sharing it: `share`)
   // 64 per wavefront keeps the wavefront count where fir_filter is disturbed least (128-sample tiles, 17.5 K of them:
   // 32 → fir 0.160 ms per launch, 64 → 0.149 ms, same whole-job rate).
-  int lpw = (unsigned long long)n_tiles * share > 12288ull ? 64 : 32;
-  {
-    static const char *const e = getenv("LSDR_RX_LANES");   // tuning hook: tiles per wavefront
-    if (e) lpw = atoi(e);
-    if (lpw < 1 || (lpw > 32 && lpw != 64)) lpw = (unsigned long long)n_tiles * share > 12288ull ? 64 : 32;   // (estimator groups: ≤ 32, or two of 32)
-    a.lanes_per_wave = (unsigned)lpw;
-    static const char *const d = LSDR_MEASURE_ENV("LSDR_RX_DBG");   // measure build only: timing-only tiles
-    static const bool prio = getenv("LSDR_RX_PRIO") && atoi(getenv("LSDR_RX_PRIO"));
-    a.dbg = (d ? (unsigned)atoi(d) & 3u : 0u) | (prio ? 4u : 0u);
-  }
-  // nearest / linear sampler: the tiles' samples are staged through LDS (see rx_tile_tol) — cu8 always; cf32 when all 64 rows of a
-  // stage belong to tiles of the wavefront and the launch is small enough (≤ 1024 wavefronts) that its 9 KiB per wavefront do not
-  // decide how many are resident: C3's 4 Gi-sample batches are 8.7 K wavefronts, and next to fir_filter's 114 KiB per CU only
-  // four of them fit a CU — direct loads (no LDS) ran that chain 12 % faster.  LSDR_RX_NO_LDS=1 keeps the direct loads (A/B
-  // measurements), =2 for cf32 input only
-  static const int no_lds = getenv("LSDR_RX_NO_LDS") ? atoi(getenv("LSDR_RX_NO_LDS")) : 0;
-  const bool lds_fmt = r->cfg.in_format == LSDR_IN_CU8 ? (no_lds != 1 && r->omega <= 8.f)
-                                                       : (no_lds == 0 && lpw == 64 && (unsigned long long)n_tiles * share <= 65536ull &&
-                                                          ((unsigned long long)in & 7ull) == 0);
-  const bool use_lds = r->cfg.sampler != LSDR_SAMP_FIR && lds_fmt;
-  const unsigned blocks = 1 + (n_tiles - 1 + (unsigned)lpw - 1) / (unsigned)lpw;
-  P->n_tiles = n_tiles; P->blocks = blocks; P->lpw = (unsigned)lpw; P->stage_stride = stage_stride; P->sym_per_chunk = sym_per_chunk;
+  // The tuning hook's value holds where the estimator groups allow it: ≤ 32, or two of 32.
+  const bool lanes_ok = H.lanes >= 1 && (H.lanes <= 32 || H.lanes == 64);
+  const unsigned lpw = lanes_ok ? (unsigned)H.lanes : (unsigned long long)n_tiles * share > 12288ull ? 64u : 32u;
+  a.lanes_per_wave = lpw;
+  a.dbg = H.dbg | (H.prio ? 4u : 0u);
+  if (!cu8) use_lds = use_lds && lpw == 64 && (unsigned long long)n_tiles * share <= 65536ull && ((unsigned long long)in & 7ull) == 0;
+  const unsigned blocks = 1 + (n_tiles - 1 + lpw - 1) / lpw;
+  P->n_tiles = n_tiles; P->blocks = blocks; P->lpw = lpw; P->stage_stride = stage_stride; P->sym_per_chunk = sym_per_chunk;
   P->hpitch = hpitch; P->hard = hard;
-  if (hard && !(use_lds && r->cfg.in_format == LSDR_IN_CU8)) { lsdr_set_error("cstln_receiver: LSDR_SYM_HARD2 needs cu8 input with the nearest or linear sampler"); return LSDR_E_UNSUPPORTED; }
+  if (hard && !(use_lds && cu8)) { lsdr_set_error("cstln_receiver: LSDR_SYM_HARD2 needs cu8 input with the nearest or linear sampler"); return LSDR_E_UNSUPPORTED; }
   // k_rx_compact_h lets a partial output word be finished by the NEXT tile from the previous tile's column only: every tile must
   // hold at least two words' worth of symbols (32) after a dropped first one
   if (hard && (float)Lc * kChunk / (r->omega + 0.1f) < 34.f) {
@@ -1661,61 +1664,72 @@ static int rx_tiled_plan(lsdr_rx *r, unsigned share, const void *in, size_t n_in
   return LSDR_OK;
 }
 
-static int rx_tiled_launch(lsdr_rx *r, const rx_plan &P) {
+// The k_rx_tiles instantiation of a launch.  S: sampler (2: FIR, whose tiles are never staged through LDS — and never write hard
+// symbols: rx_tiled_plan refuses that).  Hard symbols come from staged cu8 tiles only.
+typedef void (*rx_tiles_kernel_t)(rx_tiled_multi);
+template <int S, bool A>
+static rx_tiles_kernel_t rx_tiles_of(bool cu8, bool use_lds, bool hard) {
+  constexpr bool L = S != 2;
+  if (hard) return k_rx_tiles<S, A, LSDR_IN_CU8, L, L>;
+  if (use_lds) return cu8 ? k_rx_tiles<S, A, LSDR_IN_CU8, L, false> : k_rx_tiles<S, A, LSDR_IN_CF32, L, false>;
+  return cu8 ? k_rx_tiles<S, A, LSDR_IN_CU8, false, false> : k_rx_tiles<S, A, LSDR_IN_CF32, false, false>;
+}
+static rx_tiles_kernel_t rx_kernel_tiles(int sampler, bool arith, bool cu8, bool use_lds, bool hard) {
+  switch (sampler) {
+    case LSDR_SAMP_NEAREST: return arith ? rx_tiles_of<0, true>(cu8, use_lds, hard) : rx_tiles_of<0, false>(cu8, use_lds, hard);
+    case LSDR_SAMP_LINEAR: return arith ? rx_tiles_of<1, true>(cu8, use_lds, hard) : rx_tiles_of<1, false>(cu8, use_lds, hard);
+  }
+  return arith ? rx_tiles_of<2, true>(cu8, use_lds, hard) : rx_tiles_of<2, false>(cu8, use_lds, hard);
+}
+
+// One run of each of rs[0..n), planned alike (rx_tiled_enqueue_multi's tests), in shared launches on their common stream: block row
+// i of every launch is receiver i.  What only a receiver on its own has — the FIR sampler's tap refresh, the timing events, hard
+// symbols, a measurement stream — goes with n == 1.
+static int rx_tiled_launch(lsdr_rx *const *rs, const rx_plan *P, unsigned n) {
+  lsdr_rx *r = rs[0];
   lsdr_ctx *c = r->ctx;
-  const rx_tiled_args &a = P.a;
-  const unsigned blocks = P.blocks, n_tiles = P.n_tiles, stage_stride = P.stage_stride, sym_per_chunk = P.sym_per_chunk;
-  const unsigned long long hpitch = P.hpitch;
-  const bool hard = P.hard, use_lds = P.use_lds, want_meas = P.want_meas;
-  const size_t nm = P.nm;
-  const int lpw = (int)P.lpw, slot = P.slot;
-  lsdr_softsymbol *const out = P.out;
-  rx_tiled_multi tm1;
-  for (int i = 0; i < kRxMulti; ++i) tm1.a[i] = a;
-#define LSDR_RX_LAUNCH_F(S, A, F, L, H) hipLaunchKernelGGL((k_rx_tiles<S, A, F, L, H>), dim3(blocks), dim3(64), 0, c->stream, tm1)
-#define LSDR_RX_LAUNCH(S, A) do { if (hard) LSDR_RX_LAUNCH_F(S, A, LSDR_IN_CU8, (S != 2), (S != 2)); \
-                                  else if (use_lds && r->cfg.in_format == LSDR_IN_CU8) LSDR_RX_LAUNCH_F(S, A, LSDR_IN_CU8, (S != 2), false); \
-                                  else if (use_lds) LSDR_RX_LAUNCH_F(S, A, LSDR_IN_CF32, (S != 2), false); \
-                                  else if (r->cfg.in_format == LSDR_IN_CU8) LSDR_RX_LAUNCH_F(S, A, LSDR_IN_CU8, false, false); \
-                                  else LSDR_RX_LAUNCH_F(S, A, LSDR_IN_CF32, false, false); } while (0)
-#define LSDR_RX_LAUNCH_S(S) do { if (r->qpsk_arith) LSDR_RX_LAUNCH(S, true); else LSDR_RX_LAUNCH(S, false); } while (0)
-  if (r->cfg.sampler == LSDR_SAMP_FIR)
+  const unsigned n_tiles = P[0].n_tiles, lpw = P[0].lpw, stage_stride = P[0].stage_stride;
+  const int slot = P[0].slot;
+  const bool timed = n == 1 && r->time_on;
+  rx_tiled_multi tm;
+  rx_seam_multi sm;
+  rx_ema_multi em;
+  for (unsigned i = 0; i < (unsigned)kRxMulti; ++i) {
+    const unsigned k = i < n ? i : 0;      // the records past n repeat receiver 0's
+    tm.a[i] = P[k].a;
+    sm.c[i] = rx_seam_rec{rs[k]->d_info, rs[k]->d_fix, rs[k]->d_part, rs[k]->d_stage, rs[k]->d_wstage, P[k].out, rs[k]->d_state,
+                          rs[k]->h_res_dev + P[k].slot};   // totals go straight into the pinned ring slot
+    em.c[i] = rx_ema_rec{rs[k]->d_ema_wave, rs[k]->d_ema, rs[k]->d_state_next, rs[k]->d_state};
+  }
+  if (n == 1 && r->cfg.sampler == LSDR_SAMP_FIR)
     hipLaunchKernelGGL(k_rx_fir_refresh, dim3(1), dim3(256), 0, c->stream, (const rx_state_dev *)r->d_state, (const float2 *)r->d_trig,
                        (const float *)r->d_coeffs, r->cfg.ncoeffs, r->cfg.subsampling, r->d_shifted_tol);
-  if (r->time_on) { LSDR_HIP(hipEventRecord(r->tev0[slot], c->stream)); }
-  if (r->cfg.sampler == LSDR_SAMP_NEAREST) LSDR_RX_LAUNCH_S(0);
-  else if (r->cfg.sampler == LSDR_SAMP_LINEAR) LSDR_RX_LAUNCH_S(1);
-  else LSDR_RX_LAUNCH_S(2);
-  r->tev_set[slot] = r->time_on;
-  if (r->time_on) { LSDR_HIP(hipEventRecord(r->tev1[slot], c->stream)); }
-#undef LSDR_RX_LAUNCH_S
-#undef LSDR_RX_LAUNCH
-#undef LSDR_RX_LAUNCH_F
+  if (timed) { LSDR_HIP(hipEventRecord(r->tev0[slot], c->stream)); }
+  hipLaunchKernelGGL(rx_kernel_tiles(r->cfg.sampler, r->qpsk_arith, r->cfg.in_format == LSDR_IN_CU8, P[0].use_lds, P[0].hard),
+                     dim3(P[0].blocks, n), dim3(64), 0, c->stream, tm);
+  if (n == 1) r->tev_set[slot] = timed;
+  if (timed) { LSDR_HIP(hipEventRecord(r->tev1[slot], c->stream)); }
   LSDR_HIP(hipGetLastError());
   // ---- estimators (AGC, MER) of the run — scan of the tiles' maps, installs the end state —, seam pass, compaction: all on the stream
   const int R = r->tabs.nrotations;
   const float quad = 65536.0f / R;
-  if (hard) {
-    hipLaunchKernelGGL(k_rx_ema, dim3(1), dim3(kEmaThreads), 0, c->stream, (const rx_ema_map *)r->d_ema_wave, rx_ema_groups(n_tiles, (unsigned)lpw),
-                       (const rx_ema_map *)r->d_ema, n_tiles, rx_ema_group((unsigned)lpw), (const rx_state_dev *)r->d_state_next, r->d_state,
-                       want_meas ? r->d_meas : nullptr, want_meas ? (unsigned)nm : 0u);
+  const bool meas = n == 1 && P[0].want_meas;     // (shared launches carry no measurement stream)
+  rx_meas *const d_meas = meas ? r->d_meas : nullptr;
+  const unsigned n_meas = meas ? (unsigned)P[0].nm : 0u;
+  if (P[0].hard) {
+    hipLaunchKernelGGL(k_rx_ema, dim3(1), dim3(kEmaThreads), 0, c->stream, (const rx_ema_map *)r->d_ema_wave, rx_ema_groups(n_tiles, lpw),
+                       (const rx_ema_map *)r->d_ema, n_tiles, rx_ema_group(lpw), (const rx_state_dev *)r->d_state_next, r->d_state, d_meas, n_meas);
     hipLaunchKernelGGL(k_rx_seam_h, dim3((n_tiles + kSeamBlock - 1) / kSeamBlock), dim3(kSeamBlock), 0, c->stream,
                        (const rx_tile_info_h *)r->d_hinfo, r->d_fix, n_tiles, r->omega, R, quad, r->d_part, (const uint8_t *)r->d_relabel);
-    hipLaunchKernelGGL((k_rx_compact_h<rx_state_dev>), dim3((n_tiles + 63) / 64), dim3(64), 0, c->stream, (const unsigned *)r->d_hstage, hpitch,
+    hipLaunchKernelGGL((k_rx_compact_h<rx_state_dev>), dim3((n_tiles + 63) / 64), dim3(64), 0, c->stream, (const unsigned *)r->d_hstage, P[0].hpitch,
                        (const rx_tile_info_h *)r->d_hinfo, (const rx_tile_fix *)r->d_fix, (const rx_seam_part *)r->d_part,
-                       (const uint8_t *)r->d_relabel, n_tiles, R, quad, reinterpret_cast<unsigned *>(out),
+                       (const uint8_t *)r->d_relabel, n_tiles, R, quad, reinterpret_cast<unsigned *>(P[0].out),
                        (unsigned long long)r->out_sym_offset, r->d_state, r->h_res_dev + slot);
   } else {
-    rx_seam_multi sm;
-    rx_ema_multi em;
-    for (int i = 0; i < kRxMulti; ++i) {
-      sm.c[i] = rx_seam_rec{r->d_info, r->d_fix, r->d_part, r->d_stage, r->d_wstage, out, r->d_state, r->h_res_dev + slot};   // totals go straight into the pinned ring slot
-      em.c[i] = rx_ema_rec{r->d_ema_wave, r->d_ema, r->d_state_next, r->d_state};
-    }
-    hipLaunchKernelGGL(k_rx_seam_ema_multi, dim3((n_tiles + kSeamBlock - 1) / kSeamBlock + 1, 1), dim3(kSeamBlock), 0, c->stream, sm, em, n_tiles,
-                       r->omega, R, quad, stage_stride, sym_per_chunk, (const uint8_t *)r->d_relabel, rx_ema_groups(n_tiles, (unsigned)lpw),
-                       rx_ema_group((unsigned)lpw), want_meas ? r->d_meas : nullptr, want_meas ? (unsigned)nm : 0u);
-    hipLaunchKernelGGL(k_rx_compact_multi, dim3((n_tiles + kCompactTiles - 1) / kCompactTiles, 1), dim3(64), 0, c->stream, sm, n_tiles, R, quad,
+    hipLaunchKernelGGL(k_rx_seam_ema_multi, dim3((n_tiles + kSeamBlock - 1) / kSeamBlock + 1, n), dim3(kSeamBlock), 0, c->stream, sm, em, n_tiles,
+                       r->omega, R, quad, stage_stride, P[0].sym_per_chunk, (const uint8_t *)r->d_relabel, rx_ema_groups(n_tiles, lpw),
+                       rx_ema_group(lpw), d_meas, n_meas);
+    hipLaunchKernelGGL(k_rx_compact_multi, dim3((n_tiles + kCompactTiles - 1) / kCompactTiles, n), dim3(64), 0, c->stream, sm, n_tiles, R, quad,
                        stage_stride, (const uint8_t *)r->d_relabel);
   }
   LSDR_HIP(hipGetLastError());
@@ -1750,7 +1764,7 @@ static int rx_tiled_enqueue(lsdr_rx *r, const void *in, size_t n_in, lsdr_softsy
   rx_plan P;
   LSDR_TRY(rx_tiled_plan(r, 1u, in, n_in, out, cap_out, want_meas, meas_cap, cstln_cap, &P));
   if (chunks_out) *chunks_out = P.chunks;
-  if (P.chunks) LSDR_TRY(rx_tiled_launch(r, P));
+  if (P.chunks) LSDR_TRY(rx_tiled_launch(&r, &P, 1));
   LSDR_TRY(rx_tiled_commit(r, P, r->ctx->stream, consumed));
   if (nm_out) *nm_out = P.nm;
   return LSDR_OK;
@@ -1770,7 +1784,7 @@ static int rx_tiled_enqueue_multi(lsdr_rx *const *rs, unsigned n, const void *co
     alike = a->ctx == b->ctx && a->cfg.sampler == b->cfg.sampler && a->cfg.in_format == b->cfg.in_format &&
             a->cfg.out_format == b->cfg.out_format && a->cfg.tile_len == b->cfg.tile_len && a->cfg.tile_warmup == b->cfg.tile_warmup &&
             a->cfg.cstln == b->cfg.cstln && a->omega == b->omega && a->qpsk_arith == b->qpsk_arith && a->cfg.ncoeffs == b->cfg.ncoeffs &&
-            a->cfg.subsampling == b->cfg.subsampling && a->tabs.nrotations == b->tabs.nrotations;
+            a->cfg.subsampling == b->cfg.subsampling && a->tabs.nrotations == b->tabs.nrotations && a->time_on == b->time_on;
   }
   if (alike) alike = rs[0]->cfg.out_format != LSDR_SYM_HARD2 && rs[0]->cfg.sampler != LSDR_SAMP_FIR && !rs[0]->time_on;
   std::vector<rx_plan> Pv(n);
@@ -1781,51 +1795,13 @@ static int rx_tiled_enqueue_multi(lsdr_rx *const *rs, unsigned n, const void *co
             P[i].stage_stride == P[0].stage_stride && P[i].use_lds == P[0].use_lds;
   if (!alike || !P[0].chunks) {      // receiver by receiver, from the plans
     for (unsigned i = 0; i < n; ++i) {
-      if (P[i].chunks) LSDR_TRY(rx_tiled_launch(rs[i], P[i]));
+      if (P[i].chunks) LSDR_TRY(rx_tiled_launch(&rs[i], &P[i], 1));
       LSDR_TRY(rx_tiled_commit(rs[i], P[i], rs[i]->ctx->stream, &consumed[i]));
     }
     return LSDR_OK;
   }
-  lsdr_rx *r = rs[0];
-  lsdr_ctx *c = r->ctx;
-  static const bool skip = LSDR_MEASURE_ENV("LSDR_RX_SKIP") != nullptr;     // measure build only: no receiver kernels at all (results are garbage)
-  if (skip) {
-    for (unsigned i = 0; i < n; ++i) LSDR_TRY(rx_tiled_commit(rs[i], P[i], c->stream, &consumed[i]));
-    return LSDR_OK;
-  }
-  rx_tiled_multi tm;
-  rx_ema_multi em;
-  rx_seam_multi sm;
-  for (unsigned i = 0; i < n; ++i) {
-    tm.a[i] = P[i].a;
-    em.c[i] = rx_ema_rec{rs[i]->d_ema_wave, rs[i]->d_ema, rs[i]->d_state_next, rs[i]->d_state};
-    sm.c[i] = rx_seam_rec{rs[i]->d_info, rs[i]->d_fix, rs[i]->d_part, rs[i]->d_stage, rs[i]->d_wstage, outs[i], rs[i]->d_state,
-                          rs[i]->h_res_dev + P[i].slot};
-  }
-  for (unsigned i = n; i < (unsigned)kRxMulti; ++i) { tm.a[i] = P[0].a; em.c[i] = em.c[0]; sm.c[i] = sm.c[0]; }
-  const unsigned blocks = P[0].blocks, n_tiles = P[0].n_tiles;
-  const bool use_lds = P[0].use_lds;
-#define LSDR_RXM_LAUNCH_F(S, A, F, L) hipLaunchKernelGGL((k_rx_tiles<S, A, F, L, false>), dim3(blocks, n), dim3(64), 0, c->stream, tm)
-#define LSDR_RXM_LAUNCH(S, A) do { if (use_lds && r->cfg.in_format == LSDR_IN_CU8) LSDR_RXM_LAUNCH_F(S, A, LSDR_IN_CU8, true); \
-                                   else if (use_lds) LSDR_RXM_LAUNCH_F(S, A, LSDR_IN_CF32, true); \
-                                   else if (r->cfg.in_format == LSDR_IN_CU8) LSDR_RXM_LAUNCH_F(S, A, LSDR_IN_CU8, false); \
-                                   else LSDR_RXM_LAUNCH_F(S, A, LSDR_IN_CF32, false); } while (0)
-#define LSDR_RXM_LAUNCH_S(S) do { if (r->qpsk_arith) LSDR_RXM_LAUNCH(S, true); else LSDR_RXM_LAUNCH(S, false); } while (0)
-  if (r->cfg.sampler == LSDR_SAMP_NEAREST) LSDR_RXM_LAUNCH_S(0);
-  else LSDR_RXM_LAUNCH_S(1);
-#undef LSDR_RXM_LAUNCH_S
-#undef LSDR_RXM_LAUNCH
-#undef LSDR_RXM_LAUNCH_F
-  LSDR_HIP(hipGetLastError());
-  const int R = r->tabs.nrotations;
-  const float quad = 65536.0f / R;
-  hipLaunchKernelGGL(k_rx_seam_ema_multi, dim3((n_tiles + kSeamBlock - 1) / kSeamBlock + 1, n), dim3(kSeamBlock), 0, c->stream, sm, em, n_tiles, r->omega,
-                     R, quad, P[0].stage_stride, P[0].sym_per_chunk, (const uint8_t *)r->d_relabel, rx_ema_groups(n_tiles, P[0].lpw),
-                     rx_ema_group(P[0].lpw), (rx_meas *)nullptr, 0u);
-  hipLaunchKernelGGL(k_rx_compact_multi, dim3((n_tiles + kCompactTiles - 1) / kCompactTiles, n), dim3(64), 0, c->stream, sm, n_tiles, R, quad,
-                     P[0].stage_stride, (const uint8_t *)r->d_relabel);
-  LSDR_HIP(hipGetLastError());
-  for (unsigned i = 0; i < n; ++i) LSDR_TRY(rx_tiled_commit(rs[i], P[i], c->stream, &consumed[i]));
+  if (!rx_env().skip) LSDR_TRY(rx_tiled_launch(rs, P, n));
+  for (unsigned i = 0; i < n; ++i) LSDR_TRY(rx_tiled_commit(rs[i], P[i], rs[0]->ctx->stream, &consumed[i]));
   return LSDR_OK;
 }
 
@@ -1847,6 +1823,19 @@ static int rx_tiled_wait(lsdr_rx *r, size_t *produced) {
   return LSDR_OK;
 }
 
+// n measurement records on the device → the caller's FREQ / SS / MER streams (each may be null)
+static int rx_meas_export(const rx_meas *d_meas, size_t n, float *freq_out, float *ss_out, float *mer_out) {
+  if (!n) return LSDR_OK;
+  std::vector<rx_meas> m(n);
+  LSDR_HIP(hipMemcpy(m.data(), d_meas, n * sizeof(rx_meas), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) {
+    if (freq_out) freq_out[i] = m[i].freqw / 65536;                   // freq_tap
+    if (ss_out) ss_out[i] = sqrtf(m[i].est_insp);                      // sdr.h:910
+    if (mer_out) mer_out[i] = m[i].est_ep ? 10 * logf(m[i].est_sp / m[i].est_ep) / logf(10) : 0;  // sdr.h:912
+  }
+  return LSDR_OK;
+}
+
 static int rx_run_tiled(lsdr_rx *r, const void *in, size_t n_in, lsdr_softsymbol *out, size_t cap_out,
                         size_t *consumed, size_t *produced, float *freq_out, float *ss_out, float *mer_out,
                         size_t meas_cap, size_t *n_meas, lsdr_cf32 *cstln_out, size_t cstln_cap, size_t *n_cstln) {
@@ -1859,15 +1848,7 @@ static int rx_run_tiled(lsdr_rx *r, const void *in, size_t n_in, lsdr_softsymbol
   if (rc) return rc;
   rc = rx_pull_state(r);
   if (rc) return rc;
-  if (want_meas && nm) {
-    std::vector<rx_meas> m(nm);
-    LSDR_HIP(hipMemcpy(m.data(), r->d_meas, nm * sizeof(rx_meas), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < nm; ++i) {
-      if (freq_out) freq_out[i] = m[i].freqw / 65536;
-      if (ss_out) ss_out[i] = sqrtf(m[i].est_insp);
-      if (mer_out) mer_out[i] = m[i].est_ep ? 10 * logf(m[i].est_sp / m[i].est_ep) / logf(10) : 0;
-    }
-  }
+  if (want_meas) LSDR_TRY(rx_meas_export(r->d_meas, nm, freq_out, ss_out, mer_out));
   if (n_meas) *n_meas = want_meas ? nm : 0;
   if (cstln_out && cstln_cap && chunks) {     // one point per chunk that produced a symbol, in stream order
     std::vector<float2> pts(chunks);
@@ -2190,16 +2171,8 @@ int lsdr_rx_run(lsdr_rx *r, const void *in, size_t n_in, lsdr_softsymbol *out, s
   size_t eff_meas_cap = want_meas ? (meas_cap < need_meas ? meas_cap : need_meas) : need_meas;
   size_t need_cstln = max_chunks + 1;
   size_t eff_cstln_cap = cstln_out ? (cstln_cap < need_cstln ? cstln_cap : need_cstln) : need_cstln;
-  if (r->meas_cap < need_meas) {
-    (void)hipFree(r->d_meas);
-    LSDR_HIP(hipMalloc((void **)&r->d_meas, need_meas * sizeof(rx_meas)));
-    r->meas_cap = need_meas;
-  }
-  if (cstln_out && r->cstln_cap < need_cstln) {
-    (void)hipFree(r->d_cstln);
-    LSDR_HIP(hipMalloc((void **)&r->d_cstln, need_cstln * sizeof(float2)));
-    r->cstln_cap = need_cstln;
-  }
+  LSDR_TRY(rx_grow(&r->d_meas, &r->meas_cap, need_meas));
+  if (cstln_out) LSDR_TRY(rx_grow(&r->d_cstln, &r->cstln_cap, need_cstln));
   int rc = rx_push_state(r);
   if (rc) return rc;
 
@@ -2231,15 +2204,7 @@ int lsdr_rx_run(lsdr_rx *r, const void *in, size_t n_in, lsdr_softsymbol *out, s
   LSDR_HIP(hipStreamSynchronize(c->stream));
   *consumed = cnt[0];
   *produced = cnt[1];
-  if (want_meas && cnt[2]) {
-    std::vector<rx_meas> m(cnt[2]);
-    LSDR_HIP(hipMemcpy(m.data(), r->d_meas, cnt[2] * sizeof(rx_meas), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < cnt[2]; ++i) {
-      if (freq_out) freq_out[i] = m[i].freqw / 65536;                   // freq_tap
-      if (ss_out) ss_out[i] = sqrtf(m[i].est_insp);                      // sdr.h:910
-      if (mer_out) mer_out[i] = m[i].est_ep ? 10 * logf(m[i].est_sp / m[i].est_ep) / logf(10) : 0;  // sdr.h:912
-    }
-  }
+  if (want_meas) LSDR_TRY(rx_meas_export(r->d_meas, (size_t)cnt[2], freq_out, ss_out, mer_out));
   if (n_meas) *n_meas = want_meas ? cnt[2] : 0;
   if (cstln_out && cnt[3]) LSDR_HIP(hipMemcpy(cstln_out, r->d_cstln, cnt[3] * sizeof(float2), hipMemcpyDeviceToHost));
   if (n_cstln) *n_cstln = cstln_out ? cnt[3] : 0;

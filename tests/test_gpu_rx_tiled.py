@@ -239,6 +239,39 @@ def test_tiled_fir_sampler_taps_in_lds_or_hbm_same_as_serial(capi, ctx, oracle, 
     assert rep["pass"], (rep, TOL)
 
 
+def _queued_runs(capi, ctx, kws, sts, dins, m, isz, multi, half=16000, timed=()):
+    """One receiver per entry of `kws`, started from sts[k] on the capture dins[k] (m samples of isz bytes): two queued runs of
+    half + 1 samples each, through lsdr_rx_run_multi_async (multi) or receiver by receiver.  The receivers in `timed` have their
+    tile timing switched on.  Returns the samples consumed and, per receiver, (symbols of both runs, tiled_stats(), final state,
+    timed k_rx_tiles launches)."""
+    rxs = [capi.CstlnReceiver(ctx, **k) for k in kws]
+    dins = dins[:len(rxs)]
+    for r, st in zip(rxs, sts):
+        r.set_state(st)
+    for k in timed:
+        rxs[k].tile_time(True)
+    outs = [[ctx.alloc(m * 4 + 1024) for _ in range(2)] for _ in rxs]
+    pos = 0
+    for q in range(2):
+        if multi:
+            used = capi.CstlnReceiver.run_multi_async(rxs, [d.at(pos * isz) for d in dins], half + 1, [o[q].ptr for o in outs], m)
+            assert len(used) == len(rxs) and len(set(used)) == 1       # one entry per capture; alike receivers take the same
+            used = used[0]
+        else:
+            for r, d, o in zip(rxs, dins, outs):
+                used = r.run_async(d.at(pos * isz), half + 1, o[q].ptr, m)
+        pos += used
+    res = []
+    for r, o in zip(rxs, outs):
+        syms = [ctx.download(o[q], capi.SOFTSYM, r.wait()).copy() for q in range(2)]
+        res.append((syms, r.tiled_stats(), r.state().as_dict(), r.tile_time(False)[1]))
+        r.close()
+    for o in outs:
+        for b in o:
+            b.free()
+    return pos, res
+
+
 @pytest.mark.parametrize("fmt", ["cf32", "cu8"])
 def test_multi_capture_runs_equal_separate_queued_runs(capi, ctx, oracle, fmt):
     """lsdr_rx_run_multi_async: three independent captures (own signal, own loop state) share their launches — same symbols,
@@ -266,29 +299,7 @@ def test_multi_capture_runs_equal_separate_queued_runs(capi, ctx, oracle, fmt):
     half = 16000
 
     def run(multi, kws):
-        rxs = [capi.CstlnReceiver(ctx, **k) for k in kws]
-        for r, st in zip(rxs, sts):
-            r.set_state(st)
-        outs = [[ctx.alloc(m * 4 + 1024) for _ in range(2)] for _ in rxs]
-        pos = 0
-        for q in range(2):
-            if multi:
-                used = capi.CstlnReceiver.run_multi_async(rxs, [d.at(pos * isz) for d in dins], half + 1, [o[q].ptr for o in outs], m)
-                assert len(used) == len(rxs) and len(set(used)) == 1       # one entry per capture; alike receivers take the same
-                used = used[0]
-            else:
-                for r, d, o in zip(rxs, dins, outs):
-                    used = r.run_async(d.at(pos * isz), half + 1, o[q].ptr, m)
-            pos += used
-        res = []
-        for r, o in zip(rxs, outs):
-            syms = [ctx.download(o[q], capi.SOFTSYM, r.wait()).copy() for q in range(2)]
-            res.append((syms, r.tiled_stats(), r.state().as_dict()))
-            r.close()
-        for o in outs:
-            for b in o:
-                b.free()
-        return pos, res
+        return _queued_runs(capi, ctx, kws, sts, dins, m, isz, multi, half)
 
     pos_a, sep = run(False, [kw] * 3)
     pos_b, mul = run(True, [kw] * 3)
@@ -307,6 +318,44 @@ def test_multi_capture_runs_equal_separate_queued_runs(capi, ctx, oracle, fmt):
             assert bits_equal(mixed[k][0][q], mixed_sep[k][0][q]), (k, q)
     for d in dins:
         d.free()
+
+
+@pytest.fixture(scope="module")
+def nine_captures(capi, ctx):
+    """Nine cf32 captures of 69 000 samples (own signal, own SNR), each acquired by the serial receiver over its first 32768
+    samples, and what nine receivers queued one by one with lsdr_rx_run_async make of the rest: the reference of every group below."""
+    kw = dict(sampler=capi.SAMP_LINEAR, cstln=capi.QPSK, omega=4.0, mode=capi.RX_TILED, tile_len=256, tile_warmup=256)
+    sts, dins = [], []
+    for k in range(9):
+        x, _ = synth.qpsk_baseband(69000, 4, seed=20 + k, rms=50.0, snr_db=18.0 + k)
+        acq = capi.CstlnReceiver(ctx, sampler=capi.SAMP_LINEAR, cstln=capi.QPSK, omega=4.0)
+        acq.run(x[:32768], meas=False)
+        sts.append(acq.state()); acq.close()
+        dins.append(ctx.upload(x[32768:]))
+    m = 69000 - 32768
+    pos, sep = _queued_runs(capi, ctx, [kw] * 9, sts, dins, m, 8, False)
+    yield dict(kw=kw, sts=sts, dins=dins, m=m, pos=pos, sep=sep)
+    for d in dins:
+        d.free()
+
+
+@pytest.mark.parametrize("n,timed", [(1, ()), (8, ()), (9, ()), (3, (1,))], ids=["one", "full", "one_too_many", "one_timed"])
+def test_group_sizes_of_shared_launches_equal_separate_queued_runs(capi, ctx, nine_captures, n, timed):
+    """The edges of lsdr_rx_run_multi_async's grouping, over two queued runs of 16 001 samples (more than one wavefront
+    of tiles each): a single receiver (the trivial group), eight (every record of a shared launch in use), nine (one more than
+    a launch holds: queued one by one), and three of which receiver 1 has its tile timing on — a timed receiver's tiles are
+    launched on their own between its events, so nothing is shared and the two launches are timed.  Every receiver consumes the
+    same and ends with the symbols, counts, seam statistics and loop state of its separate lsdr_rx_run_async calls, bit for bit."""
+    c = nine_captures
+    pos, got = _queued_runs(capi, ctx, [c["kw"]] * n, c["sts"], c["dins"], c["m"], 8, True, timed=timed)
+    assert pos == c["pos"] == 2 * 16000 and len(got) == n
+    for k in range(n):
+        syms, stats, state, launches = got[k]
+        want = c["sep"][k]
+        for q in range(2):
+            assert len(syms[q]) > 3000 and bits_equal(syms[q], want[0][q]), (k, q)       # (wait() returned the same count)
+        assert stats == want[1] and stats["tiles"] > 32 and state == want[2], k
+        assert launches == (2 if k in timed else 0), (k, launches)
 
 
 _STAGED_SCRIPT = r"""
