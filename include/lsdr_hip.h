@@ -774,7 +774,7 @@ int lsdr_capture_batch_tile_time(lsdr_capture_batch *b, int enable, float *avg_m
 /* Signal reports: per capture what `leandvb --fd-info` prints — cstln_receiver writes FREQ, SS and MER once per meas_decimation samples
  * (sdr.h:857-913: the estimators est_insp / est_sp / est_ep of sdr.h:866-889, freqw behind the drift clamp of sdr.h:895-898; leandvb.cc:428-430,
  * 465, 502, 600-605; leandvb's period is Fs/Finfo).  They tell a weak capture (MER) from a mistuned one (FREQ, held inside
- * ± 65536/omega/2048 table units per sample around 0) and from one at the wrong level (SS: the LEVEL CONTRACT below asks for about 75).
+ * ± 65536/omega/2048 table units per sample around the capture's tune — 0 in a uniform run, lsdr_capture_each below) and from one at the wrong level (SS: the LEVEL CONTRACT below asks for about 75).
  * Both engines, all sample formats, in the batch's own launches: the tiles fold each body chunk's estimator inputs into an affine map
  * per tile (a chunk belongs to exactly one tile's body; the error vector is taken at the serial gain the tile estimates, as the soft
  * records are), one more launch per batch composes the maps of every capture from the constructed estimators, and the records follow the
@@ -840,7 +840,8 @@ int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev,
  *    transposed and compacted into one contiguous u8 array per capture, its count in device memory.  Tile 0 runs from the constructed
  *    state: its symbols are the reference's bit for bit.  Tile j ≥ 1 starts tile_warmup samples early at mu = phase = 0 with the
  *    CONSTRUCTED frequency word (`freq`) and is held within ± 65536 / omega / 2048 of it (4.07e-4 cycles per sample at omega 1.2) — the
- *    contract of both tiled receivers: A CAPTURE MUST BE TUNED TO WITHIN THAT WINDOW OF ITS CARRIER (`freq`, leandvb's --tune).
+ *    contract of both tiled receivers: A CAPTURE MUST BE TUNED TO WITHIN THAT WINDOW OF ITS CARRIER (`freq`, leandvb's --tune);
+ *    per capture: lsdr_hs_each_run_async below.
  *  * dvb_deconvol_sync: all four alignments are scored on the chunks ≡ 0 (mod resync_period); the score uses the second half of a
  *    chunk's words only, so it carries no history, and for a freshly constructed block the alignment in force while chunk c is decoded is
  *    c == 0 ? 0 : first arg-min of the scores of chunk ((c − 1) / P)·P — a function of the symbol stream, evaluated per thread.
@@ -873,6 +874,38 @@ const uint8_t *lsdr_hs_batch_ts_dev(const lsdr_hs_batch *b, int i);        /* de
 const uint8_t *lsdr_hs_batch_symbols_dev(const lsdr_hs_batch *b, int i);   /* its hard symbols, one per byte (result.symbols of them) */
 const uint8_t *lsdr_hs_batch_bytes_dev(const lsdr_hs_batch *b, int i);     /* dvb_deconvol_sync's output, mpeg_sync's output */
 const uint8_t *lsdr_hs_batch_mpeg_dev(const lsdr_hs_batch *b, int i);
+
+/* ------------------------------------------------------------ per-capture lengths and --tune in one batch
+ * The recordings of a job never have equal lengths, and a capture the reports show as mistuned (FREQ) needs leandvb's --tune
+ * (demod.set_freq(Ftune/Fs), leandvb.cc:483-487, 817-821).  An EACH run gives every capture of a batch its own length and its own tune;
+ * tune is GIVEN by the caller exactly as --tune is — nothing here estimates it.
+ *  * Capture i of an each run is decoded as a freshly constructed graph with set_freq(each[i].tune) over its first each[i].n_samples items.
+ *    wait, the TS download, the accessors, reports and viterbi_stats work as before; every result is per capture: in lsdr_capture_result
+ *    samples, tiles, symbols and seam_* are that capture's own, as are the packed words / soft symbols, the report slots and the final
+ *    record (result.samples / period reports), the detected bins (the detect points inside that capture) and the Viterbi bytes.
+ *  * COMPOSITION INVARIANCE: what capture i produces does not depend on the other captures of the batch — bit for bit the TS, every field
+ *    of lsdr_capture_result, packed words and soft symbols, report slots and final record, detected bins, Viterbi bytes.  (The launches
+ *    are sized for the longest capture; every kernel leaves by the capture's own counts.  With anf = 1 the notch instantiation of the
+ *    tiles runs when ANY capture has a detect point; a capture without one passes through it unchanged.)
+ *  * The uniform entry points (lsdr_capture_batch_run_async, lsdr_capture_any_run_async, lsdr_hs_batch_run_async) are the each path with
+ *    equal lengths and tune = 0 (capture batch) or tune = cfg.freq (hs batch); their outputs are what they were.
+ *  * In the hs batch each[i].tune replaces cfg.freq for that capture.
+ *  * iq_dev[i] may be NULL only where n_samples is 0 (a valid capture that decodes nothing).  Alignment per item, and 16 bytes with
+ *    anf = 1, as for the uniform calls.  The non-cu8 objects (lsdr_capture_any_create) go through the same call: hence `void`.
+ *  * THE TUNING CONTRACT with tune in it: tiles j >= 1 start from the frequency word constructed for tune and are held within
+ *    +- 65536/omega/2048 table units per sample of it (4.07e-4 cycles per sample at omega 1.2), so THE CARRIER MUST LIE WITHIN THAT WINDOW
+ *    OF tune; the hs batch has its own window of the same width around tune.  FREQ reports are held inside that window around tune, no
+ *    longer around 0; the drift clamp (sdr.h:895-898) is the reference's, around tune as well.
+ * LSDR_E_ARG, with a message, the object left usable: n_samples > max_samples, tune not finite or |tune| >= 0.5, nonzero reserved, a
+ * batch in flight. */
+typedef struct {
+  size_t n_samples;   /* this capture's length, <= cfg.max_samples; 0 is valid (nothing decoded) */
+  float  tune;        /* set_freq(Ftune/Fs) for this capture, cycles per sample, sign as lsdr_hs_batch_cfg.freq / lsdr_fastqpsk_create:
+                         a capture multiplied by exp(+j2π·f·n) is tuned with +f */
+  int    reserved[5]; /* 0 */
+} lsdr_capture_each;   /* 32 bytes */
+int lsdr_capture_each_run_async(lsdr_capture_batch *b, const void *const *iq_dev, const lsdr_capture_each *each /* [B], host */);
+int lsdr_hs_each_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, const lsdr_capture_each *each /* [B], host */);
 
 #ifdef __cplusplus
 }

@@ -354,6 +354,15 @@ class HsBatchCfg(C.Structure):
 
 
 _sig("lsdr_hs_batch_create", C.c_int, [vp, C.POINTER(HsBatchCfg), C.POINTER(vp)])
+
+
+class CaptureEach(C.Structure):
+    """lsdr_capture_each: one capture's length and tune in an `each` run."""
+    _fields_ = [("n_samples", C.c_size_t), ("tune", C.c_float), ("reserved", C.c_int * 5)]
+
+
+_sig("lsdr_capture_each_run_async", C.c_int, [vp, vp, C.POINTER(CaptureEach)])
+_sig("lsdr_hs_each_run_async", C.c_int, [vp, vp, C.POINTER(CaptureEach)])
 _sig("lsdr_hs_batch_destroy", None, [vp])
 _sig("lsdr_hs_batch_run_async", C.c_int, [vp, vp, c_sz])
 _sig("lsdr_hs_batch_wait", C.c_int, [vp, vp])
@@ -857,10 +866,10 @@ class _TailBatch:
     """What the objects in front of the device-resident FEC tail share (CaptureBatch, HsBatch): a batch of self.n captures through
     run_async / wait, the TS download, and fetching TS and stage bytes.  A subclass sets _what, its name in error texts, and _c, the
     prefix of its C entry points (<_c>_wait, _ts_download_async, _ts_wait, _ts_dev, _bytes_dev, _mpeg_dev and _destroy), and hands its
-    handle and its run_async entry point to _attach."""
+    handle, its run_async entry point and its `each` entry point (per-capture lengths and tunes, lsdr_capture_each) to _attach."""
 
-    def _attach(self, h, run):
-        self.h, self._run = h, run
+    def _attach(self, h, run, run_each):
+        self.h, self._run, self._run_each = h, run, run_each
         self._res = (CaptureResult * max(self.n, 1))()
 
     def _fn(self, name):
@@ -876,6 +885,25 @@ class _TailBatch:
 
     def run_async(self, iq_ptrs, n_samples):
         check(self._run(self.h, self._ptrs(iq_ptrs), int(n_samples)))
+
+    def each(self, n_samples, tune=None):
+        """The lsdr_capture_each array of a batch: n_samples a list (one length per capture), tune None (the uniform call's: 0, or the
+        hs batch's freq), a scalar for all captures or a list."""
+        n = [int(v) for v in n_samples]
+        if tune is None:
+            tune = getattr(self, "freq", 0.0)
+        t = [float(tune)] * self.n if np.isscalar(tune) else [float(v) for v in tune]
+        if len(n) != self.n or len(t) != self.n:
+            raise LsdrError(f"{self._what}: {len(n)} lengths and {len(t)} tunes for {self.n} captures")
+        e = (CaptureEach * max(self.n, 1))()
+        for i in range(self.n):
+            e[i].n_samples, e[i].tune = n[i], t[i]
+        return e
+
+    def run_each_async(self, iq_ptrs, n_samples, tune=None):
+        """run_async with a length (and a tune, leandvb's --tune as Ftune/Fs in cycles per sample) per capture; a pointer may be None where
+        the length is 0."""
+        check(self._run_each(self.h, self._ptrs(iq_ptrs), self.each(n_samples, tune)))
 
     def wait(self, results=True):
         check(self._fn("wait")(self.h, self._res if results else None))
@@ -901,10 +929,18 @@ class _TailBatch:
     def decode(self, iq_ptrs, n_samples):
         """One batch, synchronously: (results, [TS bytes per capture])."""
         self.run_async(iq_ptrs, n_samples)
+        return self._results_and_ts()
+
+    def _results_and_ts(self):
         res = self.wait()
         out = [self._fetch(self._fn("ts_dev")(self.h, i), r["ts_packets"] * 188, sync=False) for i, r in enumerate(res)]
         self.ctx.sync()
         return res, [a.tobytes() for a in out]
+
+    def decode_each(self, iq_ptrs, n_samples, tune=None):
+        """decode with a length and a tune per capture (run_each_async)."""
+        self.run_each_async(iq_ptrs, n_samples, tune)
+        return self._results_and_ts()
 
     def stage_bytes(self, i, which, n):
         """The first n bytes in front of mpeg_sync ("deconv") or behind it ("mpeg") of capture i after a run (host)."""
@@ -943,7 +979,7 @@ class CaptureBatch(_TailBatch):
             check(lib.lsdr_capture_batch_create_viterbi(ctx.h, C.byref(cfg), C.byref(vcfg), C.byref(h)))
         else:
             check(lib.lsdr_capture_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
-        self._attach(h, lib.lsdr_capture_any_run_async if self._any else lib.lsdr_capture_batch_run_async)
+        self._attach(h, lib.lsdr_capture_any_run_async if self._any else lib.lsdr_capture_batch_run_async, lib.lsdr_capture_each_run_async)
         if reports:
             try:
                 self.set_reports(reports)
@@ -1027,7 +1063,8 @@ class HsBatch(_TailBatch):
         cfg.allow_drift, cfg.fastlock, cfg.tile_len, cfg.tile_warmup = int(allow_drift), int(fastlock), tile_len, tile_warmup
         h = vp()
         check(lib.lsdr_hs_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
-        self._attach(h, lib.lsdr_hs_batch_run_async)
+        self.freq = float(freq)
+        self._attach(h, lib.lsdr_hs_batch_run_async, lib.lsdr_hs_each_run_async)
 
     def symbols_ptr(self, i):
         """Device pointer of capture i's hard symbols, one per byte (None for i out of range)."""

@@ -25,7 +25,7 @@ struct lsdr_capture_batch {
   lsdr_rxb *rx;
   lsdr_tail *tail;
   bool in_flight;
-  size_t consumed;
+  std::vector<size_t> consumed;    // per capture, of the last batch
   // the Viterbi engine (vb != null)
   lsdr_viterbi_batch *vb;
   size_t soft_cap, byte_cap;
@@ -160,11 +160,14 @@ int lsdr_capture_batch_create_viterbi(lsdr_ctx *c, const lsdr_capture_batch_cfg 
   return lsdr_capture_any_create(c, cfg, vcfg ? vcfg : &v, nullptr, out);
 }
 
-int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev, size_t n_samples) {
-  LSDR_ARG(b && iq_dev);
+// one batch, capture i over its first n_samples[i] items with set_freq(tune[i]): what every run_async entry point comes to
+static int capture_batch_run(lsdr_capture_batch *b, const void *const *iq_dev, const size_t *n_samples, const float *tune) {
   if (b->in_flight) { lsdr_set_error("capture_batch: a batch is in flight (lsdr_capture_batch_wait first)"); return LSDR_E_ARG; }
   if (b->vb) LSDR_TRY(lsdr_viterbi_batch_reset(b->vb, -1));              // every capture: a freshly constructed viterbi_sync
-  LSDR_TRY(lsdr_rxb_launch(b->rx, iq_dev, n_samples, &b->consumed, b->ctx_aux ? b->ctx_aux->stream : nullptr));
+  std::vector<size_t> consumed(b->cfg.n_captures, 0);
+  // (the front end checks every capture's arguments before it queues anything: a refused batch leaves the object usable)
+  LSDR_TRY(lsdr_rxb_launch(b->rx, iq_dev, n_samples, tune, consumed.data(), b->ctx_aux ? b->ctx_aux->stream : nullptr));
+  b->consumed = consumed;
   if (b->vb) {
     const std::vector<unsigned long long> zero(b->cfg.n_captures, 0ull);
     LSDR_TRY(capture_batch_viterbi_round(b, true, zero, zero, zero));
@@ -174,6 +177,27 @@ int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev,
   }
   b->in_flight = true;
   return LSDR_OK;
+}
+
+int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev, size_t n_samples) {
+  LSDR_ARG(b && iq_dev);
+  for (int i = 0; i < b->cfg.n_captures; ++i) LSDR_ARG(iq_dev[i]);
+  const std::vector<size_t> n(b->cfg.n_captures, n_samples);
+  const std::vector<float> tune(b->cfg.n_captures, 0.f);
+  return capture_batch_run(b, iq_dev, n.data(), tune.data());
+}
+
+int lsdr_capture_each_run_async(lsdr_capture_batch *b, const void *const *iq_dev, const lsdr_capture_each *each) {
+  LSDR_ARG(b && iq_dev && each);
+  const int B = b->cfg.n_captures;
+  std::vector<size_t> n(B);
+  std::vector<float> tune(B);
+  for (int i = 0; i < B; ++i) {
+    for (int q = 0; q < 5; ++q)
+      if (each[i].reserved[q]) { lsdr_set_error("capture_batch: capture %d: lsdr_capture_each.reserved must be 0", i); return LSDR_E_ARG; }
+    n[i] = each[i].n_samples; tune[i] = each[i].tune;
+  }
+  return capture_batch_run(b, iq_dev, n.data(), tune.data());
 }
 
 int lsdr_capture_batch_run_async(lsdr_capture_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples) {
@@ -218,8 +242,8 @@ int lsdr_capture_batch_wait(lsdr_capture_batch *b, lsdr_capture_result *results)
   b->in_flight = false;
   for (int i = 0; results && i < b->cfg.n_captures; ++i) {
     lsdr_capture_result &r = results[i];
-    r.samples = b->consumed;
-    r.tiles = lsdr_rxb_tiles(b->rx);
+    r.samples = b->consumed[i];
+    r.tiles = lsdr_rxb_tiles(b->rx, (unsigned)i);
     unsigned long long tot = 0; unsigned d = 0, m = 0, bad = 0;
     LSDR_TRY(lsdr_rxb_seam_stats(b->rx, (unsigned)i, &tot, &d, &m, &bad));
     r.seam_dup = d; r.seam_miss = m; r.seam_bad = bad;

@@ -30,9 +30,16 @@ struct hsb_rec {                   // per capture, device memory; copied to pinn
   unsigned long long chunks;       // deconvolver chunks decoded
 };
 
+struct hsb_each {                  // per capture and run, device memory (uploaded by run_async): what lsdr_capture_each sets
+  unsigned long long total_chunks; // 128-sample chunks of this capture
+  unsigned n_tiles, pad;
+  long long freqw, min_freqw, max_freqw;   // the constructed fq_state under set_freq(its tune)
+};
+
 struct hsb_args {
-  fq_tiled_args t;                 // tables, loop constants, tile geometry, freq_window (in / stage / info / state unused)
-  fq_state st0;                    // fast_qpsk_receiver as constructed
+  fq_tiled_args t;                 // tables, loop constants, tile lengths, freq_window (in / stage / info / state / total_chunks / n_tiles unused)
+  fq_state st0;                    // fast_qpsk_receiver as constructed, but for what set_freq sets (hsb_each)
+  const hsb_each *each;            // [B]
   const unsigned char *const *in;  // [B] cu8 captures
   unsigned *stage;                 // [B][rows][pitch] dwords
   unsigned rows, pitch;
@@ -74,15 +81,17 @@ __device__ __forceinline__ void hsb_tiles_body(const hsb_args &A, const unsigned
     if (blockIdx.x == 0) { if (threadIdx.x != 0) return; j = 0; }
     else j = 1u + (blockIdx.x - 1u) * 64u + threadIdx.x;
   }
-  if (j >= a0.n_tiles) return;
+  const hsb_each each = A.each[cap];
+  if (j >= each.n_tiles) return;
   fq_tiled_args a = a0;
   if (LDSRECT) a.rect = rect_lds;
-  const unsigned long long first = a.first_chunks, Lc = a.tile_chunks, Wc = a.warm_chunks, total = a.total_chunks;
+  const unsigned long long first = a.first_chunks, Lc = a.tile_chunks, Wc = a.warm_chunks, total = each.total_chunks;
   unsigned long long cb, c0, c1;
   if (j == 0) { cb = 0; c0 = 0; c1 = first; }
   else { c0 = first + (unsigned long long)(j - 1) * Lc; c1 = c0 + Lc; cb = c0 - Wc; }
   if (c1 > total) c1 = total;
   fq_state s = A.st0;
+  s.freqw = each.freqw; s.min_freqw = each.min_freqw; s.max_freqw = each.max_freqw;
   rx_tile_info_h ti;
   ti.has_pre = 0; ti.n_warm = 0; ti.warm_tail = 0; ti.body_tail = 0; ti.mu_begin = ti.phase_begin = 0.f;
   const long long f_lo = s.freqw - a.freq_window, f_hi = s.freqw + a.freq_window;
@@ -129,15 +138,16 @@ __global__ __launch_bounds__(kHsbLdsWaves * 64) void k_hsb_tiles_lds(hsb_args A)
 }
 
 __global__ __launch_bounds__(kSeamBlock) void k_hsb_seam(hsb_args A) {
-  const unsigned cap = blockIdx.y;
-  rx_seam_h_body(A.info + (unsigned long long)cap * A.tiles_cap, A.fix + (unsigned long long)cap * A.tiles_cap, A.t.n_tiles, A.t.omega, 4,
+  const unsigned cap = blockIdx.y, n_tiles = A.each[cap].n_tiles;
+  if (blockIdx.x * kSeamBlock >= n_tiles) return;
+  rx_seam_h_body(A.info + (unsigned long long)cap * A.tiles_cap, A.fix + (unsigned long long)cap * A.tiles_cap, n_tiles, A.t.omega, 4,
                  16384.0f, A.part + (unsigned long long)cap * A.parts_cap, A.relabel);
 }
 
 constexpr unsigned kHsbTile = 64;            // tiles and staging rows per compaction workgroup
 static_assert(kSeamBlock % kHsbTile == 0, "the tiles of a compaction workgroup share their seam block");
 __global__ __launch_bounds__(256) void k_hsb_compact(hsb_args A, unsigned row_blocks) {
-  const unsigned cap = blockIdx.y, n_tiles = A.t.n_tiles;
+  const unsigned cap = blockIdx.y, n_tiles = A.each[cap].n_tiles;
   const unsigned grp = blockIdx.x / row_blocks, rb = blockIdx.x - grp * row_blocks;
   const unsigned j0 = grp * kHsbTile, r0 = rb * kHsbTile;
   if (j0 >= n_tiles) return;

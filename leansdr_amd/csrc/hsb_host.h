@@ -15,9 +15,11 @@ struct lsdr_hs_batch {
   const unsigned char **d_in, **h_in;        // [B] capture pointers: device copy, pinned staging
   unsigned char **d_bytes;
   hsb_rec *d_rec, *h_rec;                    // h_rec pinned
+  hsb_each *d_each, *h_each;                 // [B] per-capture geometry and tuning of a run: device copy, pinned staging
+  float max_omega;
   bool in_flight;
   int lds_rect;                              // tile kernel with the rect table in LDS: 1 / 0 forced, −1 by the size of the run
-  size_t consumed; unsigned tiles;
+  std::vector<size_t> consumed; std::vector<unsigned> tiles;   // per capture, of the last run
   std::vector<void *> owned;
 };
 
@@ -35,6 +37,13 @@ static unsigned hsb_tiles_of(const lsdr_hs_batch *b, size_t chunks) {
   return n;
 }
 
+// fast_qpsk_receiver::set_freq (sdr.h:981-986): the frequency word and the limits update_freq_limits puts around it
+static void hsb_set_freq(const lsdr_hs_batch *b, float freq, long long &freqw, long long &min_freqw, long long &max_freqw) {
+  freqw = (long long)(freq * 65536);
+  min_freqw = (long long)((float)freqw - 65536 / b->max_omega / 8);
+  max_freqw = (long long)((float)freqw + 65536 / b->max_omega / 8);
+}
+
 static int hsb_build(lsdr_hs_batch *b) {
   lsdr_ctx *c = b->ctx;
   const lsdr_hs_batch_cfg &cfg = b->cfg;
@@ -45,9 +54,8 @@ static int hsb_build(lsdr_hs_batch *b) {
   fq_state st;
   memset(&st, 0, sizeof(st));
   const float tol = 10e-6, max_omega = omega * (1 + tol);
-  st.freqw = (long long)(cfg.freq * 65536);
-  st.min_freqw = (long long)((float)st.freqw - 65536 / max_omega / 8);
-  st.max_freqw = (long long)((float)st.freqw + 65536 / max_omega / 8);
+  b->max_omega = max_omega;
+  hsb_set_freq(b, cfg.freq, st.freqw, st.min_freqw, st.max_freqw);
   const long long freq_beta = (long long)(0.0012 * 256 * 65536 / (double)omega * 1.0);
   if (freq_beta == 0) { lsdr_set_error("fast_qpsk_receiver: Excessive oversampling"); return LSDR_E_ARG; }
   // geometry: lsdr_fastqpsk_set_tiled's defaults
@@ -121,8 +129,13 @@ static int hsb_build(lsdr_hs_batch *b) {
   LSDR_HIP(hipMemset(b->d_rec, 0, (size_t)B * sizeof(hsb_rec)));
   LSDR_HIP(hipHostMalloc((void **)&b->h_in, (size_t)B * sizeof(void *), hipHostMallocDefault));
   LSDR_HIP(hipHostMalloc((void **)&b->h_rec, (size_t)B * sizeof(hsb_rec), hipHostMallocDefault));
+  LSDR_TRY(hsb_alloc(b, (void **)&b->d_each, (size_t)B * sizeof(hsb_each)));
+  LSDR_HIP(hipMemset(b->d_each, 0, (size_t)B * sizeof(hsb_each)));
+  LSDR_HIP(hipHostMalloc((void **)&b->h_each, (size_t)B * sizeof(hsb_each), hipHostMallocDefault));
+  memset(b->h_each, 0, (size_t)B * sizeof(hsb_each));
+  b->consumed.assign(B, 0); b->tiles.assign(B, 0);
   memset(b->h_rec, 0, (size_t)B * sizeof(hsb_rec));
-  A.in = b->d_in; A.rec = b->d_rec; A.bytes = b->d_bytes;
+  A.in = b->d_in; A.rec = b->d_rec; A.bytes = b->d_bytes; A.each = b->d_each;
   A.vit = lsdr_tail_vit_dev(b->tail);
   {
     std::vector<unsigned char *> bytes(B);
@@ -150,6 +163,7 @@ void lsdr_hs_batch_destroy(lsdr_hs_batch *b) {
   for (void *p : b->owned) (void)hipFree(p);
   if (b->h_in) (void)hipHostFree(b->h_in);
   if (b->h_rec) (void)hipHostFree(b->h_rec);
+  if (b->h_each) (void)hipHostFree(b->h_each);
   delete b;
 }
 
@@ -166,23 +180,34 @@ int lsdr_hs_batch_create(lsdr_ctx *c, const lsdr_hs_batch_cfg *cfg, lsdr_hs_batc
   return LSDR_OK;
 }
 
-int lsdr_hs_batch_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples) {
-  LSDR_ARG(b && iq_dev);
-  LSDR_ARG(n_samples <= b->cfg.max_samples);
-  for (int i = 0; i < b->cfg.n_captures; ++i) LSDR_ARG(iq_dev[i] || n_samples == 0);
+// one batch, capture i over its first n_samples[i] items with set_freq(tune[i]): what both run_async entry points come to
+static int hsb_run(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, const size_t *n_samples, const float *tune) {
+  const unsigned B = (unsigned)b->cfg.n_captures;
+  for (unsigned i = 0; i < B; ++i) {
+    if (n_samples[i] > b->cfg.max_samples) { lsdr_set_error("hs_batch: capture %u has %zu samples, created for %zu", i, n_samples[i], b->cfg.max_samples); return LSDR_E_ARG; }
+    if (!iq_dev[i] && n_samples[i]) { lsdr_set_error("hs_batch: capture %u has no samples pointer", i); return LSDR_E_ARG; }
+  }
   if (b->in_flight) { lsdr_set_error("hs_batch: a batch is in flight (lsdr_hs_batch_wait first)"); return LSDR_E_ARG; }
   lsdr_ctx *c = b->ctx;
   LSDR_HIP(hipSetDevice(c->device));
-  const unsigned B = (unsigned)b->cfg.n_captures;
-  const size_t chunks = n_samples >= (size_t)(kChunk + 1) ? (n_samples - 1) / kChunk : 0;      // 129 samples for a chunk, sdr.h:1010-1013
-  const unsigned n_tiles = hsb_tiles_of(b, chunks);
-  hsb_args A = b->A;
-  A.t.total_chunks = chunks; A.t.n_tiles = n_tiles;
+  unsigned n_tiles = 0;                                                  // the longest capture's: the grids are sized for it
+  unsigned long long sum_tiles = 0;
+  for (unsigned i = 0; i < B; ++i) {
+    const size_t chunks = n_samples[i] >= (size_t)(kChunk + 1) ? (n_samples[i] - 1) / kChunk : 0;      // 129 samples for a chunk, sdr.h:1010-1013
+    hsb_each &e = b->h_each[i];
+    e.total_chunks = chunks; e.n_tiles = hsb_tiles_of(b, chunks); e.pad = 0;
+    hsb_set_freq(b, tune[i], e.freqw, e.min_freqw, e.max_freqw);
+    b->consumed[i] = chunks * kChunk; b->tiles[i] = e.n_tiles;
+    if (e.n_tiles > n_tiles) n_tiles = e.n_tiles;
+    sum_tiles += e.n_tiles;
+    b->h_in[i] = reinterpret_cast<const unsigned char *>(iq_dev[i]);
+  }
+  const hsb_args &A = b->A;
   hipLaunchKernelGGL(k_hsb_reset, dim3((B + 63) / 64), dim3(64), 0, c->stream, A, B);
   if (n_tiles) {
-    for (unsigned i = 0; i < B; ++i) { b->h_in[i] = reinterpret_cast<const unsigned char *>(iq_dev[i]); }
     LSDR_HIP(hipMemcpyAsync(b->d_in, b->h_in, B * sizeof(void *), hipMemcpyHostToDevice, c->stream));
-    const bool lds = b->lds_rect >= 0 ? b->lds_rect != 0 : (unsigned long long)B * n_tiles >= (unsigned long long)c->num_cu * (kHsbLdsWaves * 64 / 2);
+    LSDR_HIP(hipMemcpyAsync(b->d_each, b->h_each, B * sizeof(hsb_each), hipMemcpyHostToDevice, c->stream));
+    const bool lds = b->lds_rect >= 0 ? b->lds_rect != 0 : sum_tiles >= (unsigned long long)c->num_cu * (kHsbLdsWaves * 64 / 2);
     if (lds)
       hipLaunchKernelGGL(k_hsb_tiles_lds, dim3((n_tiles + kHsbLdsWaves * 64 - 1) / (kHsbLdsWaves * 64), B), dim3(kHsbLdsWaves * 64), 65536 * 2, c->stream, A);
     else
@@ -201,9 +226,30 @@ int lsdr_hs_batch_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, siz
   // the records go to the host in front of the tail, whose kernels only read them: the tail's "batch done" event is behind everything wait reads
   LSDR_HIP(hipMemcpyAsync(b->h_rec, b->d_rec, B * sizeof(hsb_rec), hipMemcpyDeviceToHost, c->stream));
   LSDR_TRY(lsdr_tail_launch(b->tail));
-  b->consumed = chunks * kChunk; b->tiles = n_tiles;
   b->in_flight = true;
   return LSDR_OK;
+}
+
+int lsdr_hs_batch_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, size_t n_samples) {
+  LSDR_ARG(b && iq_dev);
+  LSDR_ARG(n_samples <= b->cfg.max_samples);
+  const std::vector<size_t> n(b->cfg.n_captures, n_samples);
+  const std::vector<float> tune(b->cfg.n_captures, b->cfg.freq);
+  return hsb_run(b, iq_dev, n.data(), tune.data());
+}
+
+int lsdr_hs_each_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, const lsdr_capture_each *each) {
+  LSDR_ARG(b && iq_dev && each);
+  const int B = b->cfg.n_captures;
+  std::vector<size_t> n(B);
+  std::vector<float> tune(B);
+  for (int i = 0; i < B; ++i) {
+    for (int q = 0; q < 5; ++q)
+      if (each[i].reserved[q]) { lsdr_set_error("hs_batch: capture %d: lsdr_capture_each.reserved must be 0", i); return LSDR_E_ARG; }
+    if (!std::isfinite(each[i].tune) || !(fabsf(each[i].tune) < 0.5f)) { lsdr_set_error("hs_batch: capture %d: tune must be finite and inside (-0.5, 0.5) cycles per sample", i); return LSDR_E_ARG; }
+    n[i] = each[i].n_samples; tune[i] = each[i].tune;
+  }
+  return hsb_run(b, iq_dev, n.data(), tune.data());
 }
 
 int lsdr_hs_batch_wait(lsdr_hs_batch *b, lsdr_capture_result *results) {
@@ -213,8 +259,8 @@ int lsdr_hs_batch_wait(lsdr_hs_batch *b, lsdr_capture_result *results) {
   b->in_flight = false;
   for (int i = 0; results && i < b->cfg.n_captures; ++i) {
     lsdr_capture_result &r = results[i];
-    r.samples = b->consumed;
-    r.tiles = b->tiles;
+    r.samples = b->consumed[i];
+    r.tiles = b->tiles[i];
     r.seam_dup = b->h_rec[i].ndup; r.seam_miss = b->h_rec[i].nmiss; r.seam_bad = b->h_rec[i].nbad;
   }
   return LSDR_OK;

@@ -94,14 +94,15 @@ int lsdr_fir_stream_iv_launch(lsdr_ctx *c, const void *in, size_t n_in, lsdr_cf3
 struct lsdr_rxb;
 int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, int in_format, float in_scale, lsdr_rxb **out);
 void lsdr_rxb_destroy(lsdr_rxb *b);
-int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t *consumed, hipStream_t aux = nullptr);
+int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, const size_t *n_samples /* [n] */, const float *tune /* [n] */, size_t *consumed /* [n] */,
+                    hipStream_t aux = nullptr);
 const uint32_t *lsdr_rxb_words(const lsdr_rxb *b, unsigned i);
 size_t lsdr_rxb_words_cap(const lsdr_rxb *b);
 const lsdr_softsymbol *lsdr_rxb_soft(const lsdr_rxb *b, unsigned i);
 size_t lsdr_rxb_soft_cap(const lsdr_rxb *b);
 const unsigned long long *lsdr_rxb_counts_dev(const lsdr_rxb *b);
 const void *lsdr_rxb_results_dev(const lsdr_rxb *b, size_t *stride);
-unsigned lsdr_rxb_tiles(const lsdr_rxb *b);
+unsigned lsdr_rxb_tiles(const lsdr_rxb *b, unsigned i);
 int lsdr_rxb_bins(lsdr_rxb *b, unsigned i, int *bins, unsigned cap, unsigned *n);
 int lsdr_rxb_seam_stats(lsdr_rxb *b, unsigned i, unsigned long long *total, unsigned *dup, unsigned *miss, unsigned *bad);
 int lsdr_rxb_tile_time(lsdr_rxb *b, int enable, float *avg_ms, unsigned *launches);

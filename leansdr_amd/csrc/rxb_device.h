@@ -61,6 +61,7 @@ struct rxb_cap {
   unsigned *spre;                      // [n_tiles] the warm-up's last symbol, as a soft record (the one a seam may re-insert)
   unsigned *out_soft;                  // the capture's compacted soft symbols
   unsigned long long *count_out;       // → the capture's entry of a contiguous uint64[n_captures]: symbols in out_soft
+  const rx_state_dev *state0;          // the capture's loop state right after construction: set_freq(its tune) (lsdr_capture_each)
 };
 
 // Signal reports of one capture (`--fd-info`: cstln_receiver writes FREQ / SS / MER once per meas_decimation samples, sdr.h:857-913).
@@ -74,10 +75,10 @@ struct rxb_rep {
 
 struct rxb_args {
   const rxb_cap *caps;
-  const unsigned *iv_of_block;         // [blocks of 4096 samples] detect interval a block belongs to (the same for every capture)
+  // both tables depend on the block index only: built for the longest capture of a launch, they are a prefix every shorter one reads its own part of
+  const unsigned *iv_of_block;         // [blocks of 4096 samples] detect interval a block belongs to
   const unsigned *det_block;           // [n_det] block index of every detect point
   const float2 *om;                    // reverse-FFT twiddles (notch_detect.h)
-  const rx_state_dev *state0;          // loop state right after construction (every capture starts there)
   unsigned tile_chunks, warm_chunks;
   unsigned pre_block, pre_look;        // samples per pre-pass block; blocks a tile looks back
   float nk, l2omk;                     // auto_notch::k, log2(1 − k)
@@ -243,6 +244,8 @@ __global__ __launch_bounds__(256) void k_rxb_notch_pre(rxb_args A) {
 }
 
 // ---- tiles -------------------------------------------------------------------------------------------------------------------------
+// a value every lane of the wavefront has, moved into a scalar register
+__device__ __forceinline__ float rxb_uniform(float v) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
 // atan(u)·65536/2π for |u| ≤ 1, odd polynomial (max error 2e-6 rad = 0.02 table units)
 __host__ __device__ __forceinline__ float rxb_atan_units(float u) {
   const float S = 10430.3784f;
@@ -393,9 +396,11 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
   const char *const row = lds + lane * kRowBytes + delta;                   // sample s0 of the stage in flight sits here
 
   const rx_consts &C = A.C;
-  const rx_state_dev *S0 = A.state0;
-  float freqw = S0->freqw, agc = S0->agc_gain, est_insp = S0->est_insp;
-  const float min_f = S0->min_freqw, max_f = S0->max_freqw;
+  // the capture's constructed state, read once through the pointer in its record and held in scalar registers (the same for every lane)
+  const rx_state_dev *S0 = cap.state0;
+  const float s0_freqw = rxb_uniform(S0->freqw), s0_insp = rxb_uniform(S0->est_insp), s0_mu = rxb_uniform(S0->mu);
+  float freqw = s0_freqw, agc = rxb_uniform(S0->agc_gain), est_insp = s0_insp;
+  const float min_f = rxb_uniform(S0->min_freqw), max_f = rxb_uniform(S0->max_freqw);
   float fwin = 65536.0f / C.omega / 2048.0f;
   if (fwin < 8.f) fwin = 8.f;
   const float f_lo = freqw - fwin, f_hi = freqw + fwin;
@@ -404,7 +409,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
   // symbol timing at the tile's first sample, predicted from the capture's first sample (mu = 0 there) at the nominal omega: see rx_tile_tol
   float mu = 0.f, phase = 0.f;
   {
-    const double ws = (double)cb * kChunk - (double)S0->mu, om = (double)C.omega;
+    const double ws = (double)cb * kChunk - (double)s0_mu, om = (double)C.omega;
     const double r = ws - om * __builtin_floor(ws / om);
     mu = (float)(r > 0.0 ? om - r : 0.0);
     if (!(mu >= 0.f && mu < C.omega)) mu = 0.f;
@@ -466,7 +471,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
       mu_begin = mu + over; phase_begin = phase - over * freqw;
       got = hcnt; hwarm = hacc; hnwarm = hcnt < 16u ? hcnt : 16u; hcnt = 0;
       if (GAIN && got) {
-        pavg = __builtin_fmaf(__builtin_exp2f((float)(cb + Wc) * __builtin_log2f(k1)), S0->est_insp - pavg, pavg);
+        pavg = __builtin_fmaf(__builtin_exp2f((float)(cb + Wc) * __builtin_log2f(k1)), s0_insp - pavg, pavg);
         soft_gain(pavg);
       }
     }
@@ -483,7 +488,7 @@ __device__ __forceinline__ void rxb_tile(const rxb_args &A, const rxb_cap &cap, 
     }
     const unsigned cnt0 = hcnt;
     const bool wlast = ci + 1 == nwarm;           // (SOFT: the last warm-up chunk; its symbols at the gain estimated so far)
-    if (SOFT && active && wlast) soft_gain(__builtin_fmaf(__builtin_exp2f((float)(cb + Wc) * __builtin_log2f(k1)), S0->est_insp - pavg, pavg));
+    if (SOFT && active && wlast) soft_gain(__builtin_fmaf(__builtin_exp2f((float)(cb + Wc) * __builtin_log2f(k1)), s0_insp - pavg, pavg));
     float g0r = 0.f, g0i = 0.f;                  // last interpolated sample of the chunk, before derotation (|.|² feeds the AGC)
 #pragma unroll 1
     for (int sb = 0; sb < kChunk / kStage; ++sb) {
@@ -629,7 +634,7 @@ __device__ __forceinline__ void rxb_tiles_body(const rxb_args &A) {
       a.n_tiles = cap.n_tiles; a.lanes_per_wave = 64; a.dbg = 0; a.stage_stride = 0; a.stage = nullptr; a.wstage = nullptr; a.wstride = 0;
       a.info = nullptr; a.hstage = cap.hstage; a.hpitch = cap.hpitch; a.hinfo = cap.hinfo; a.ema = cap.ema_scratch; a.ema_wave = cap.ema_scratch + 1;
       if (SOFT) a.stage = reinterpret_cast<lsdr_softsymbol *>(cap.sstage);
-      a.state = A.state0; a.state_next = cap.state_end; a.meas = nullptr; a.meas_base = 0; a.cstln = nullptr; a.C = A.C; a.T = A.T;
+      a.state = cap.state0; a.state_next = cap.state_end; a.meas = nullptr; a.meas_base = 0; a.cstln = nullptr; a.C = A.C; a.T = A.T;
       if (REP) {                                 // tile 0 owns chunks [0, warm_chunks): its slots and its (constant) map hold exact values
         a.ema_wave = A.rep[blockIdx.y].map;
         if (A.rep_period) { a.meas = A.rep[blockIdx.y].slot; a.C.meas_decimation = A.rep_period; }
@@ -690,7 +695,7 @@ __global__ __launch_bounds__(kRxbRepThreads) void k_rxb_reports(rxb_args A) {
   exl.a = __shfl_up(inc.a, 1, 64); exl.bi = __shfl_up(inc.bi, 1, 64); exl.bs = __shfl_up(inc.bs, 1, 64); exl.be = __shfl_up(inc.be, 1, 64);
   if (lane == 0) { exl.a = 1.f; exl.bi = exl.bs = exl.be = 0.f; }
   pre = ema_then(pre, exl);
-  const rx_state_dev *S0 = A.state0;
+  const rx_state_dev *S0 = cap.state0;
   float vi = pre.a * S0->est_insp + pre.bi, vs = pre.a * S0->est_sp + pre.bs, ve = pre.a * S0->est_ep + pre.be;
   for (unsigned i = lo; i < hi; ++i) {
     const rx_ema_map mi = R.map[i];

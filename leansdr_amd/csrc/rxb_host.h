@@ -3,6 +3,9 @@
 #ifndef LSDR_RXB_HOST_H
 #define LSDR_RXB_HOST_H
 
+// geometry of one capture's run over its n_samples
+struct rxb_geom { unsigned long long chunks; unsigned n_tiles, n_det, n_pre, n_blocks; };
+
 struct lsdr_rxb {
   lsdr_ctx *ctx;
   lsdr_rx *proto;                  // tables, loop constants, the constructed loop state, the relabel maps
@@ -18,11 +21,15 @@ struct lsdr_rxb {
   size_t words_cap;                // 32-bit words of packed decisions per capture
   std::vector<rxb_cap> caps;       // host copy (buffer pointers are fixed at create; in / geometry per launch)
   rxb_cap *h_caps, *d_caps;        // pinned staging, device array
-  rx_seam_result *d_res, *h_res; rx_state_dev *d_state_end, *d_state0; rx_ema_map *d_ema;   // h_res: pinned copy of d_res, filled behind every launch
+  rx_seam_result *d_res, *h_res; rx_state_dev *d_state_end; rx_ema_map *d_ema;   // h_res: pinned copy of d_res, filled behind every launch
+  rx_state_dev *d_state0, *h_state0;                                             // [n] every capture's constructed state (its tune), pinned staging
+  std::vector<float> tune_dev; bool tune_valid;                                  // the tunes d_state0 holds
   unsigned *d_iv_of_block, *d_det_block; float2 *d_om;
   std::vector<void *> owned;       // every per-capture device allocation
-  size_t geom_samples;             // n_samples the detect-point tables on the device were built for
-  unsigned n_det, n_pre, n_tiles; unsigned long long total_chunks;
+  size_t geom_samples;             // n_samples the detect-point tables on the device were built for: the longest capture's (a prefix for the others)
+  std::vector<rxb_geom> geo;      // the last launch, per capture
+  std::vector<size_t> cap_samples;
+  bool any_det;                    // … ran the detect chain
   hipEvent_t tev0, tev1; bool timing; double time_ms; unsigned time_n; bool tev_pending;
   bool soft;                       // soft symbols out (the Viterbi engine): sstage / spre / out_soft instead of hstage / out_words
   unsigned srows;                  // rows (symbol steps) of a capture's transposed soft staging
@@ -40,8 +47,6 @@ struct lsdr_rxb {
   size_t rep_pitch;                // slots per capture, the final record included
   rxb_rep *d_rep; rx_meas *d_slots, *h_slots;   // [n] records, [n·rep_pitch] slots, their pinned copy (filled behind every launch)
   std::vector<void *> rep_owned;   // the captures' map arrays
-  size_t rep_n;                    // reports per capture of the last launch
-  bool rep_none;                   // … which ran no chunk: the constructed estimators are the final record
 };
 
 static int rxb_alloc(lsdr_rxb *b, void **p, size_t bytes) {
@@ -50,8 +55,6 @@ static int rxb_alloc(lsdr_rxb *b, void **p, size_t bytes) {
   return LSDR_OK;
 }
 
-// geometry of a run over n_samples per capture
-struct rxb_geom { unsigned long long chunks; unsigned n_tiles, n_det, n_pre, n_blocks; };
 static rxb_geom rxb_geometry(const lsdr_rxb *b, size_t n_samples) {
   rxb_geom g;
   const size_t usable = b->anf ? n_samples / kDetN * kDetN : n_samples;      // auto_notch::run moves whole 4096-sample blocks (sdr.h:64-75)
@@ -61,8 +64,13 @@ static rxb_geom rxb_geometry(const lsdr_rxb *b, size_t n_samples) {
   g.n_blocks = (unsigned)(usable / kDetN);
   g.n_det = 0;
   if (b->anf) {                                                              // `phase += fft.n; if (phase >= decimation) { phase -= decimation; detect(); }`
-    long long phase = 0;
-    for (unsigned blk = 0; blk < g.n_blocks; ++blk) { phase += kDetN; if (phase >= b->notch_decimation) { phase -= b->notch_decimation; ++g.n_det; } }
+    // decimation ≥ fft.n (lsdr_rxb_create_in): phase stays in [0, decimation), so after n blocks it is n·4096 − detects·decimation —
+    // counted per capture and launch, hence not by walking the blocks
+    if (b->notch_decimation >= kDetN) g.n_det = (unsigned)((unsigned long long)g.n_blocks * kDetN / (unsigned long long)b->notch_decimation);
+    else {
+      long long phase = 0;
+      for (unsigned blk = 0; blk < g.n_blocks; ++blk) { phase += kDetN; if (phase >= b->notch_decimation) { phase -= b->notch_decimation; ++g.n_det; } }
+    }
   }
   g.n_pre = b->anf ? (unsigned)(usable / b->pre_block) : 0u;
   return g;
@@ -149,8 +157,11 @@ int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft,
   LSDR_HIP(hipHostMalloc((void **)&b->h_res, b->n * sizeof(rx_seam_result), hipHostMallocDefault));
   memset(b->h_res, 0, b->n * sizeof(rx_seam_result));
   LSDR_HIP(hipMalloc((void **)&b->d_state_end, b->n * sizeof(rx_state_dev)));
-  LSDR_HIP(hipMalloc((void **)&b->d_state0, sizeof(rx_state_dev)));
-  LSDR_HIP(hipMemcpy(b->d_state0, &proto->st_initial, sizeof(rx_state_dev), hipMemcpyHostToDevice));
+  LSDR_HIP(hipMalloc((void **)&b->d_state0, b->n * sizeof(rx_state_dev)));
+  LSDR_HIP(hipHostMalloc((void **)&b->h_state0, b->n * sizeof(rx_state_dev), hipHostMallocDefault));
+  for (unsigned i = 0; i < b->n; ++i) b->h_state0[i] = proto->st_initial;
+  b->tune_dev.assign(b->n, 0.f); b->tune_valid = false;
+  b->geo.assign(b->n, rxb_geom()); b->cap_samples.assign(b->n, 0); b->any_det = false;
   LSDR_HIP(hipMalloc((void **)&b->d_ema, 2 * b->n * sizeof(rx_ema_map)));
   LSDR_HIP(hipMalloc((void **)&b->d_counts, b->n * sizeof(unsigned long long)));
   LSDR_HIP(hipMemset(b->d_counts, 0, b->n * sizeof(unsigned long long)));
@@ -177,7 +188,7 @@ int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft,
     }
     cp.count_out = b->d_counts + i;
     cp.res = b->d_res + i; cp.state_end = b->d_state_end + i; cp.ema_scratch = b->d_ema + 2 * i;
-    cp.hpitch = b->hpitch;
+    cp.hpitch = b->hpitch; cp.state0 = b->d_state0 + i;
     if (b->anf) {
       LSDR_TRY(rxb_alloc(b, (void **)&cp.iv, (size_t)(b->max_det + 1) * sizeof(rxb_iv)));
       LSDR_TRY(rxb_alloc(b, (void **)&cp.T, (size_t)(b->max_pre + 1) * sizeof(float2)));
@@ -199,7 +210,7 @@ static void rxb_reports_free(lsdr_rxb *b) {
   if (b->d_slots) (void)hipFree(b->d_slots);
   if (b->h_slots) (void)hipHostFree(b->h_slots);
   b->d_rep = nullptr; b->d_slots = nullptr; b->h_slots = nullptr;
-  b->rep_on = false; b->rep_period = 0; b->rep_period_k = 0; b->rep_pitch = 0; b->rep_n = 0; b->rep_none = true;
+  b->rep_on = false; b->rep_period = 0; b->rep_period_k = 0; b->rep_pitch = 0;
 }
 
 // period_samples = cstln_receiver::meas_decimation; 0: off.  The previous launch of this object must have completed.  Buffers for max_samples.
@@ -240,12 +251,14 @@ int lsdr_rxb_reports(const lsdr_rxb *b, unsigned i, const lsdr_rxb_report **slot
   LSDR_ARG(b && i < b->n && slots && n && last && b->rep_on);
   static_assert(sizeof(lsdr_rxb_report) == sizeof(rx_meas) && offsetof(lsdr_rxb_report, est_ep) == offsetof(rx_meas, est_ep), "lsdr_rxb_report mirrors rx_meas");
   const rx_meas *s = b->h_slots + (size_t)i * b->rep_pitch;
-  *slots = reinterpret_cast<const lsdr_rxb_report *>(s); *n = b->rep_none ? 0 : b->rep_n;
-  if (b->rep_none) {
-    const rx_state_dev &st = b->proto->st_initial;
+  const unsigned long long chunks = b->geo[i].chunks;                          // (none: the capture's constructed estimators are the final record)
+  const size_t rep_n = chunks && b->rep_period ? (size_t)(chunks * kChunk / b->rep_period) : 0;
+  *slots = reinterpret_cast<const lsdr_rxb_report *>(s); *n = rep_n;
+  if (!chunks) {
+    const rx_state_dev &st = b->h_state0[i];
     last->freqw = st.freqw; last->est_insp = st.est_insp; last->est_sp = st.est_sp; last->est_ep = st.est_ep; last->a = 0.f; last->tile = 0;
   } else
-    memcpy(last, s + b->rep_n, sizeof(*last));
+    memcpy(last, s + rep_n, sizeof(*last));
   return LSDR_OK;
 }
 
@@ -255,7 +268,7 @@ void lsdr_rxb_destroy(lsdr_rxb *b) {
   rxb_reports_free(b);
   for (void *p : b->owned) (void)hipFree(p);
   (void)hipFree(b->d_caps); if (b->h_caps) (void)hipHostFree(b->h_caps);
-  (void)hipFree(b->d_res); if (b->h_res) (void)hipHostFree(b->h_res); (void)hipFree(b->d_state_end); (void)hipFree(b->d_state0); (void)hipFree(b->d_ema); (void)hipFree(b->d_counts);
+  (void)hipFree(b->d_res); if (b->h_res) (void)hipHostFree(b->h_res); (void)hipFree(b->d_state_end); (void)hipFree(b->d_state0); if (b->h_state0) (void)hipHostFree(b->h_state0); (void)hipFree(b->d_ema); (void)hipFree(b->d_counts);
   (void)hipFree(b->d_iv_of_block); (void)hipFree(b->d_det_block); (void)hipFree(b->d_om);
   if (b->tev0) (void)hipEventDestroy(b->tev0);
   if (b->tev1) (void)hipEventDestroy(b->tev1);
@@ -266,7 +279,7 @@ void lsdr_rxb_destroy(lsdr_rxb *b) {
 }
 
 static void rxb_fill_args(const lsdr_rxb *b, rxb_args &A) {
-  A.caps = b->d_caps; A.iv_of_block = b->d_iv_of_block; A.det_block = b->d_det_block; A.om = b->d_om; A.state0 = b->d_state0;
+  A.caps = b->d_caps; A.iv_of_block = b->d_iv_of_block; A.det_block = b->d_det_block; A.om = b->d_om;
   A.tile_chunks = b->Lc; A.warm_chunks = b->Wc; A.pre_block = b->pre_block; A.pre_look = b->pre_look;
   A.nk = b->nk; A.l2omk = (float)log2((double)(1.0f - b->nk));
   rx_fill_consts(b->proto, A.C, A.T);
@@ -316,26 +329,57 @@ static rxb_dump_kernel_t rxb_kernel_dump(int kind) {
   return kind == kRxbS8 ? k_rxb_notch_dump<kRxbS8> : kind == kRxb16 ? k_rxb_notch_dump<kRxb16> : kind == kRxbF32 ? k_rxb_notch_dump<kRxbF32> : k_rxb_notch_dump<kRxbU8>;
 }
 
+// capture i's constructed loop state under set_freq(tune): what lsdr_rx_create leaves for cfg.freq = tune (sdr.h:745-770; leandvb calls
+// set_freq only for a nonzero --tune, leandvb.cc:483-487)
+static rx_state_dev rxb_state_of(lsdr_rx *r, float tune) {
+  if (!tune) return r->st_initial;
+  const rx_state_dev keep = r->st;
+  r->st = r->st_initial;
+  rx_set_freq(r, tune, true);
+  const rx_state_dev s = r->st;
+  r->st = keep;
+  return s;
+}
+
 // Queues the whole front end of a batch: detect chain, estimator pre-pass, tiles, seam pass, compaction.  aux == nullptr: everything on
 // the context's stream.  aux: the TILES on the context's stream, everything else on `aux` (the caller's stream for the memory-bound
 // kernels — on its own compute units, lsdr_capture_batch_cfg::aux_cus), handed over by events; what follows the compaction (the FEC tail)
 // belongs on `aux` then.  The previous launch of this object must have completed (the argument records are single-buffered).
-int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t *consumed, hipStream_t aux) {
-  LSDR_ARG(b && iq && consumed);
-  if (n_samples > b->max_samples) { lsdr_set_error("capture_batch: %zu samples per capture, created for %zu", n_samples, b->max_samples); return LSDR_E_ARG; }
+// n_samples[i], tune[i]: capture i's length and set_freq (lsdr_capture_each); consumed[i]: the samples its receiver runs over.  Every
+// capture has its own geometry in its rxb_cap; the grids are sized for the longest one and a kernel leaves by the capture's own counts.
+int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, const size_t *n_samples, const float *tune, size_t *consumed, hipStream_t aux) {
+  LSDR_ARG(b && iq && n_samples && tune && consumed);
   lsdr_ctx *c = b->ctx;
   lsdr_rx *r = b->proto;
+  // everything is checked before anything of the previous launch is overwritten
+  size_t longest = 0;
+  rxb_geom gmax; memset(&gmax, 0, sizeof(gmax));
+  std::vector<rxb_geom> geo(b->n);
+  for (unsigned i = 0; i < b->n; ++i) {
+    if (n_samples[i] > b->max_samples) { lsdr_set_error("capture_batch: capture %u has %zu samples, created for %zu", i, n_samples[i], b->max_samples); return LSDR_E_ARG; }
+    if (!std::isfinite(tune[i]) || !(fabsf(tune[i]) < 0.5f)) { lsdr_set_error("capture_batch: capture %u: tune must be finite and inside (-0.5, 0.5) cycles per sample", i); return LSDR_E_ARG; }
+    if (!iq[i] && n_samples[i]) { lsdr_set_error("capture_batch: capture %u has no samples pointer", i); return LSDR_E_ARG; }
+    if (((unsigned long long)iq[i] & (unsigned long long)(b->item_bytes - 1)) != 0) { lsdr_set_error("capture_batch: capture %u is not aligned to its items", i); return LSDR_E_ARG; }
+    const rxb_geom g = rxb_geometry(b, n_samples[i]);
+    geo[i] = g;
+    if (n_samples[i] > longest) longest = n_samples[i];
+    if (g.chunks > gmax.chunks) gmax.chunks = g.chunks;
+    if (g.n_tiles > gmax.n_tiles) gmax.n_tiles = g.n_tiles;
+    if (g.n_det > gmax.n_det) gmax.n_det = g.n_det;
+    if (g.n_pre > gmax.n_pre) gmax.n_pre = g.n_pre;
+    if (g.n_blocks > gmax.n_blocks) gmax.n_blocks = g.n_blocks;
+  }
+  const bool notch = b->anf && gmax.n_det > 0;                               // the NOTCH tiles run when any capture has a detect point
+  if (notch)
+    for (unsigned i = 0; i < b->n; ++i)
+      if (((unsigned long long)iq[i] & 15ull) != 0) { lsdr_set_error("capture_batch: with the notch the captures must be 16-byte aligned"); return LSDR_E_ARG; }
   LSDR_HIP(hipSetDevice(c->device));
   if (b->tev_pending) LSDR_TRY(lsdr_rxb_tile_time(b, -1, nullptr, nullptr));   // (the previous launch has completed: collect its events)
-  const rxb_geom g = rxb_geometry(b, n_samples);
-  *consumed = (size_t)g.chunks * kChunk;
-  b->n_det = g.n_det; b->n_pre = g.n_pre; b->n_tiles = g.n_tiles; b->total_chunks = g.chunks;
-  b->rep_n = b->rep_period ? (size_t)(g.chunks * kChunk / b->rep_period) : 0; b->rep_none = !g.chunks;
-  if (b->anf && b->geom_samples != n_samples) {                               // detect points of this capture length (the same for every capture)
-    std::vector<unsigned> ivb(g.n_blocks ? g.n_blocks : 1, 0u), det(g.n_det + 1, 0u);
+  if (b->anf && b->geom_samples != longest) {                                 // detect points up to the longest capture's length
+    std::vector<unsigned> ivb(gmax.n_blocks ? gmax.n_blocks : 1, 0u), det(gmax.n_det + 1, 0u);
     long long phase = 0;
     unsigned m = 0;
-    for (unsigned blk = 0; blk < g.n_blocks; ++blk) {
+    for (unsigned blk = 0; blk < gmax.n_blocks; ++blk) {
       phase += kDetN;
       if (phase >= b->notch_decimation) { phase -= b->notch_decimation; det[m++] = blk; }
       ivb[blk] = m;
@@ -344,36 +388,45 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
     if (aux) LSDR_HIP(hipStreamSynchronize(aux));
     LSDR_HIP(hipMemcpy(b->d_iv_of_block, ivb.data(), ivb.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     LSDR_HIP(hipMemcpy(b->d_det_block, det.data(), det.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-    b->geom_samples = n_samples;
+    b->geom_samples = longest;
   }
+  bool retune = !b->tune_valid, idle = false;
   for (unsigned i = 0; i < b->n; ++i) {
-    LSDR_ARG(iq[i] && ((unsigned long long)iq[i] & (unsigned long long)(b->item_bytes - 1)) == 0);
+    const rxb_geom &g = geo[i];
+    consumed[i] = (size_t)g.chunks * kChunk;
+    b->cap_samples[i] = n_samples[i];
     rxb_cap &cp = b->caps[i];
     cp.in = static_cast<const unsigned char *>(iq[i]);
     cp.total_chunks = g.chunks; cp.n_tiles = g.n_tiles; cp.n_det = g.n_det;
     b->h_caps[i] = cp;
+    if (!g.chunks) idle = true;
+    if (b->tune_dev[i] != tune[i]) { retune = true; b->tune_dev[i] = tune[i]; b->h_state0[i] = rxb_state_of(r, tune[i]); }
   }
+  b->geo = geo; b->any_det = notch;
   const hipStream_t sa = aux ? aux : c->stream, st = c->stream;      // auxiliary kernels / tiles
   LSDR_HIP(hipMemcpyAsync(b->d_caps, b->h_caps, b->n * sizeof(rxb_cap), hipMemcpyHostToDevice, sa));
-  if (!g.chunks) {
+  if (retune) {                                                      // (a batch tuned like the one before it uploads nothing)
+    LSDR_HIP(hipMemcpyAsync(b->d_state0, b->h_state0, b->n * sizeof(rx_state_dev), hipMemcpyHostToDevice, sa));
+    b->tune_valid = true;
+  }
+  if (idle) {                                                        // a capture without a chunk is left by every kernel: its records are cleared here
     LSDR_HIP(hipMemsetAsync(b->d_res, 0, b->n * sizeof(rx_seam_result), sa));
     LSDR_HIP(hipMemsetAsync(b->d_counts, 0, b->n * sizeof(unsigned long long), sa));
+  }
+  if (!gmax.chunks) {                                                // no capture has a chunk
     LSDR_HIP(hipMemcpyAsync(b->h_res, b->d_res, b->n * sizeof(rx_seam_result), hipMemcpyDeviceToHost, sa));
     return LSDR_OK;
   }
   rxb_args A;
   rxb_fill_args(b, A);
-  const bool notch = b->anf && g.n_det > 0;
   if (notch) {
-    if (((unsigned long long)iq[0] & 15ull) != 0) { lsdr_set_error("capture_batch: with the notch the captures must be 16-byte aligned"); return LSDR_E_ARG; }
-    for (unsigned i = 1; i < b->n; ++i) LSDR_ARG(((unsigned long long)iq[i] & 15ull) == 0);
-    hipLaunchKernelGGL(rxb_kernel_detect(b->kind), dim3(2 * g.n_det, b->n), dim3(256), 0, sa, A);
-    hipLaunchKernelGGL(k_rxb_detect_peaks, dim3(g.n_det, b->n), dim3(256), 0, sa, A);
+    hipLaunchKernelGGL(rxb_kernel_detect(b->kind), dim3(2 * gmax.n_det, b->n), dim3(256), 0, sa, A);
+    hipLaunchKernelGGL(k_rxb_detect_peaks, dim3(gmax.n_det, b->n), dim3(256), 0, sa, A);
     hipLaunchKernelGGL(k_rxb_iv, dim3((b->n + 63) / 64), dim3(64), 0, sa, A, b->n);
-    hipLaunchKernelGGL(rxb_kernel_pre(b->kind), dim3(g.n_pre, b->n), dim3(256), 0, sa, A);
+    hipLaunchKernelGGL(rxb_kernel_pre(b->kind), dim3(gmax.n_pre, b->n), dim3(256), 0, sa, A);
     LSDR_HIP(hipGetLastError());
   }
-  const unsigned blocks = 1 + (g.n_tiles - 1 + 63) / 64;
+  const unsigned blocks = 1 + (gmax.n_tiles - 1 + 63) / 64;
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_pre, sa)); LSDR_HIP(hipStreamWaitEvent(st, b->ev_pre, 0)); }
   if (b->timing) { LSDR_HIP(hipEventRecord(b->tev0, st)); }
   hipLaunchKernelGGL(b->rep_on ? rxb_kernel_tiles_rep(b->kind, notch, b->soft) : rxb_kernel_tiles(b->kind, notch, b->soft), dim3(blocks, b->n), dim3(64), 0, st, A);
@@ -381,14 +434,14 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, size_t n_samples, size_t
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_tiles, st)); LSDR_HIP(hipStreamWaitEvent(sa, b->ev_tiles, 0)); }
   const int R = r->tabs.nrotations;
   const float quad = 65536.0f / R;
-  hipLaunchKernelGGL(k_rxb_seam, dim3((g.n_tiles + kSeamBlock - 1) / kSeamBlock, b->n), dim3(kSeamBlock), 0, sa, A, r->omega, R, quad,
+  hipLaunchKernelGGL(k_rxb_seam, dim3((gmax.n_tiles + kSeamBlock - 1) / kSeamBlock, b->n), dim3(kSeamBlock), 0, sa, A, r->omega, R, quad,
                      (const uint8_t *)r->d_relabel);
   if (b->soft) {
     const unsigned row_blocks = (b->srows + kRxbSoftTile - 1) / kRxbSoftTile;
-    hipLaunchKernelGGL(k_rxb_compact_soft, dim3(((g.n_tiles + kRxbSoftTile - 1) / kRxbSoftTile) * row_blocks, b->n), dim3(256), 0, sa, A, row_blocks, R, quad,
+    hipLaunchKernelGGL(k_rxb_compact_soft, dim3(((gmax.n_tiles + kRxbSoftTile - 1) / kRxbSoftTile) * row_blocks, b->n), dim3(256), 0, sa, A, row_blocks, R, quad,
                        (const uint8_t *)r->d_relabel);
   } else
-    hipLaunchKernelGGL(k_rxb_compact, dim3((g.n_tiles * kRxbCompactLanes + 63) / 64, b->n), dim3(64), 0, sa, A, R, quad, (const uint8_t *)r->d_relabel);
+    hipLaunchKernelGGL(k_rxb_compact, dim3((gmax.n_tiles * kRxbCompactLanes + 63) / 64, b->n), dim3(64), 0, sa, A, R, quad, (const uint8_t *)r->d_relabel);
   if (b->rep_on) hipLaunchKernelGGL(k_rxb_reports, dim3(b->n), dim3(kRxbRepThreads), 0, sa, A);
   LSDR_HIP(hipGetLastError());
   LSDR_HIP(hipMemcpyAsync(b->h_res, b->d_res, b->n * sizeof(rx_seam_result), hipMemcpyDeviceToHost, sa));
@@ -404,16 +457,17 @@ size_t lsdr_rxb_soft_cap(const lsdr_rxb *b) { return b && b->soft ? b->soft_cap 
 const unsigned long long *lsdr_rxb_counts_dev(const lsdr_rxb *b) { return b ? b->d_counts : nullptr; }
 // device array [n]: .total = packed decisions of capture i after the launch (struct rx_seam_result: 8-byte total first)
 const void *lsdr_rxb_results_dev(const lsdr_rxb *b, size_t *stride) { if (stride) *stride = sizeof(rx_seam_result); return b ? b->d_res : nullptr; }
-unsigned lsdr_rxb_tiles(const lsdr_rxb *b) { return b ? b->n_tiles : 0; }
+unsigned lsdr_rxb_tiles(const lsdr_rxb *b, unsigned i) { return b && i < b->n ? b->geo[i].n_tiles : 0; }
 // debugging / tests: the detected bins of capture i (synchronous)
 int lsdr_rxb_bins(lsdr_rxb *b, unsigned i, int *bins, unsigned cap, unsigned *n) {
   LSDR_ARG(b && i < b->n && n);
-  *n = b->anf ? b->n_det : 0;
+  const unsigned n_det = b->anf ? b->geo[i].n_det : 0;                        // the capture's own detect points
+  *n = n_det;
   if (!*n || !bins) return LSDR_OK;
   LSDR_HIP(hipStreamSynchronize(b->ctx->stream));
-  std::vector<int> cand((size_t)b->n_det * kDetMaxSlots);
+  std::vector<int> cand((size_t)n_det * kDetMaxSlots);
   LSDR_HIP(hipMemcpy(cand.data(), b->caps[i].cand, cand.size() * sizeof(int), hipMemcpyDeviceToHost));
-  for (unsigned q = 0; q < b->n_det && q < cap; ++q) bins[q] = cand[(size_t)q * kDetMaxSlots];
+  for (unsigned q = 0; q < n_det && q < cap; ++q) bins[q] = cand[(size_t)q * kDetMaxSlots];
   return LSDR_OK;
 }
 // seam statistics of capture i's last launch; valid once the stream has passed the launch (the caller has waited for an event behind it)
@@ -430,12 +484,13 @@ int lsdr_rxb_seam_stats(lsdr_rxb *b, unsigned i, unsigned long long *total, unsi
 int lsdr_rxb_notched(lsdr_rxb *b, unsigned i, lsdr_cf32 *out_dev, size_t n) {
   LSDR_ARG(b && i < b->n && out_dev);
   if (!b->anf || !b->geom_samples) { lsdr_set_error("capture_batch: no notch in this batch (or no run yet)"); return LSDR_E_ARG; }
-  const size_t usable = b->geom_samples / kDetN * kDetN;
+  const size_t usable = b->cap_samples[i] / kDetN * kDetN;
   if (n > usable) n = usable;
+  if (!n) return LSDR_OK;
   rxb_args A;
   rxb_fill_args(b, A);
   // (a run without a detect point launched no detect chain: the pass-through interval 0 is written here)
-  if (!b->n_det) hipLaunchKernelGGL(k_rxb_iv, dim3((b->n + 63) / 64), dim3(64), 0, b->ctx->stream, A, b->n);
+  if (!b->any_det) hipLaunchKernelGGL(k_rxb_iv, dim3((b->n + 63) / 64), dim3(64), 0, b->ctx->stream, A, b->n);
   const unsigned segs = (unsigned)((n + b->pre_block - 1) / b->pre_block);
   hipLaunchKernelGGL(rxb_kernel_dump(b->kind), dim3((segs + 63) / 64), dim3(64), 0, b->ctx->stream, A, i, (unsigned long long)n, reinterpret_cast<float2 *>(out_dev));
   LSDR_HIP(hipGetLastError());
