@@ -878,7 +878,8 @@ const uint8_t *lsdr_hs_batch_mpeg_dev(const lsdr_hs_batch *b, int i);
 /* ------------------------------------------------------------ per-capture lengths and --tune in one batch
  * The recordings of a job never have equal lengths, and a capture the reports show as mistuned (FREQ) needs leandvb's --tune
  * (demod.set_freq(Ftune/Fs), leandvb.cc:483-487, 817-821).  An EACH run gives every capture of a batch its own length and its own tune;
- * tune is GIVEN by the caller exactly as --tune is — nothing here estimates it.
+ * tune is GIVEN by the caller exactly as --tune is — nothing here estimates it; lsdr_tune_est (below) produces that number from the raw
+ * capture, in front of the decode and apart from it.
  *  * Capture i of an each run is decoded as a freshly constructed graph with set_freq(each[i].tune) over its first each[i].n_samples items.
  *    wait, the TS download, the accessors, reports and viterbi_stats work as before; every result is per capture: in lsdr_capture_result
  *    samples, tiles, symbols and seam_* are that capture's own, as are the packed words / soft symbols, the report slots and the final
@@ -906,6 +907,60 @@ typedef struct {
 } lsdr_capture_each;   /* 32 bytes */
 int lsdr_capture_each_run_async(lsdr_capture_batch *b, const void *const *iq_dev, const lsdr_capture_each *each /* [B], host */);
 int lsdr_hs_each_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, const lsdr_capture_each *each /* [B], host */);
+
+/* ------------------------------------------------------------ per-capture carrier offset, estimated (QPSK)
+ * The number lsdr_capture_each.tune wants, from the raw capture: recordings whose carriers are off by more than the tiles' window (an
+ * ordinary LNB or SDR offset is many times 4.07e-4 cycles per sample) are estimated here, then decoded with the estimates.  It runs in
+ * front of the batch decoders and touches none of their kernels; the TUNING CONTRACT above is unchanged.
+ *
+ * THE ESTIMATOR.  The fourth power of a QPSK signal carries no modulation and has a spectral line at 4·f.  For one capture of n items let
+ * M = min(blocks, n / 4096) whole blocks of N = 4096 samples, from the capture's first sample:
+ *   1 convert the samples as the capture batch's loads do: float(item − Z)·in_scale (lsdr_capture_input_cfg);
+ *   2 divide each block by its own RMS, so that level and format cannot overflow the fourth power; an all-zero block contributes zeros;
+ *   3 w = z⁴, X = FFT_N(w), rectangular window;
+ *   4 P[k] = Σ_blocks |X[k]|², summed in block order;
+ *   5 k0 = the first arg-max of P, c = P[k0], l and r its cyclic neighbours; m = sqrt(max(l, r)/c), δ = ±m/(1 + m), + when r ≥ l;
+ *     κ = k0 + δ taken into [−N/2, N/2); tune = κ/(4N) cycles per sample;
+ *   6 the sign is lsdr_capture_each.tune's: a capture multiplied by exp(+j2π·f·n) yields +f;
+ *   7 quality = c / mean(P);
+ *   8 M == 0: the record is all zeros (blocks = 0).  (So is tune and quality of a capture whose blocks are all zero: c = 0.)
+ * RANGE: |f| < 1/8 cycle per sample — the fourth power folds at 1/4.  QPSK only.  A narrow-band interferer stronger than the line wins the
+ * peak, and quality does not tell the two apart.  The estimate is taken from the capture's start; a carrier that moves is --drift's job.
+ * ACCURACY, measured on synthetic DVB-S captures (tests/test_tune_est_abi.py, tests/test_gpu_tune_est.py) with eight
+ * blocks, at 1.2, 4 and 8 samples per symbol, noise 7.5 and 18 on the cu8 scale, offsets 0 … ±0.12: |tune − f| ≤ 2.3e-6 cycles per sample,
+ * 0.6 % of the tuning window at omega 1.2 and 3.7 % of it at omega 8; the tests hold it to an eighth of the narrowest window (7.6e-6).
+ * QUALITY reads as the line's height over the spectrum's mean: 350 … 2000 on those captures, at most 3.2 on Gaussian noise alone (eight
+ * blocks); a capture below about 30 has no line worth tuning to.  The device works in float32 and agrees with a float64 restatement to
+ * 1e-6 of the peak power.
+ * A record is a pure function of the capture's own converted samples: no atomics, every sum in a fixed order — bit for bit the same alone,
+ * in any batch, and in every format that converts to the same floats (cs16 = 256·cs8 with in_scale 2^-8 is the cs8 run).
+ * run_async queues everything on the context's stream (behind lsdr_memcpy_h2d on that context) and returns: one launch over all blocks of
+ * all captures, one over the captures, the records' copy to pinned memory; no host read in between.  wait is one event synchronisation and
+ * the read of B records.  One run in flight per object.
+ * iq_dev: HOST array of B DEVICE pointers, each aligned to its item size (2, 2, 4, 4, 8 bytes for cu8, cs8, cu16, cs16, cf32; a 16-byte
+ * aligned capture is read by 16-byte loads), NULL only where n_samples[i] is 0.  Nothing behind block M − 1 of a capture is read.
+ * LSDR_E_ARG, with a message, the object (if any) left usable: n_captures < 1, in_format outside the five LSDR_IN_*, in_scale negative or
+ * not finite, blocks > 64, nonzero reserved; a misaligned pointer, samples without a pointer, run_async with a run in flight, wait with none. */
+typedef struct lsdr_tune_est lsdr_tune_est;
+typedef struct {
+  int n_captures;      /* B */
+  int in_format;       /* LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32 */
+  float in_scale;      /* as lsdr_capture_input_cfg.in_scale: 0 or 1 = none (the normalisation makes the estimate independent of it, up to rounding) */
+  unsigned blocks;     /* blocks of 4096 samples per capture, at most 64; 0 = 8 */
+  int reserved[4];     /* 0 */
+} lsdr_tune_est_cfg;
+typedef struct {
+  float tune;          /* cycles per sample: what lsdr_capture_each.tune takes */
+  float quality;       /* power[1] / mean_power */
+  uint32_t bin;        /* k0, 0 … 4095 */
+  uint32_t blocks;     /* M: the blocks that were used; 0 = no whole block, the record is all zeros */
+  float power[3];      /* l, c, r: P at k0 − 1, k0, k0 + 1 (cyclic) */
+  float mean_power;    /* mean(P) */
+} lsdr_tune_estimate;  /* 32 bytes */
+int lsdr_tune_est_create(lsdr_ctx *ctx, const lsdr_tune_est_cfg *cfg, lsdr_tune_est **e);
+void lsdr_tune_est_destroy(lsdr_tune_est *e);
+int lsdr_tune_est_run_async(lsdr_tune_est *e, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
+int lsdr_tune_est_wait(lsdr_tune_est *e, lsdr_tune_estimate *out /* [B] */);
 
 #ifdef __cplusplus
 }

@@ -373,6 +373,30 @@ _sig("lsdr_hs_batch_symbols_dev", vp, [vp, C.c_int])
 _sig("lsdr_hs_batch_bytes_dev", vp, [vp, C.c_int])
 _sig("lsdr_hs_batch_mpeg_dev", vp, [vp, C.c_int])
 
+
+class TuneEstCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("in_format", C.c_int), ("in_scale", C.c_float), ("blocks", C.c_uint), ("reserved", C.c_int * 4)]
+
+
+class TuneEstimate(C.Structure):
+    """lsdr_tune_estimate: one capture's estimated carrier offset."""
+    _fields_ = [("tune", C.c_float), ("quality", C.c_float), ("bin", C.c_uint32), ("blocks", C.c_uint32), ("power", C.c_float * 3),
+                ("mean_power", C.c_float)]
+
+    def as_dict(self):
+        return dict(tune=float(self.tune), quality=float(self.quality), bin=int(self.bin), blocks=int(self.blocks),
+                    power=[float(v) for v in self.power], mean_power=float(self.mean_power))
+
+
+_sig("lsdr_tune_est_create", C.c_int, [vp, C.POINTER(TuneEstCfg), C.POINTER(vp)])
+_sig("lsdr_tune_est_destroy", None, [vp])
+_sig("lsdr_tune_est_run_async", C.c_int, [vp, vp, psz])
+_sig("lsdr_tune_est_wait", C.c_int, [vp, C.POINTER(TuneEstimate)])
+
+#: decode_estimated's default threshold on `quality`: the geometric mean of what Gaussian noise alone reaches (3.1) and the weakest of the
+#: test captures (347), rounded (DESIGN.md §4.8)
+TUNE_MIN_QUALITY = 30.0
+
 #: every symbol include/lsdr_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [n for n in dir(lib) if n.startswith("lsdr_")]
 
@@ -862,6 +886,44 @@ class RxBatch:
         return st
 
 
+class TuneEstimator:
+    """lsdr_tune_est: the carrier offset of each of n_captures captures, estimated from the raw samples (QPSK: the spectral line of the
+    fourth power, over the first `blocks` blocks of 4096 samples) — the number the batch decoders' per-capture tune wants."""
+
+    def __init__(self, ctx, n_captures, in_format=IN_CU8, in_scale=0.0, blocks=8):
+        self.ctx, self.n, self.h = ctx, int(n_captures), None
+        cfg = TuneEstCfg()
+        cfg.n_captures, cfg.in_format, cfg.in_scale, cfg.blocks = self.n, int(in_format), float(in_scale), int(blocks)
+        h = vp()
+        check(lib.lsdr_tune_est_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self._out = (TuneEstimate * self.n)()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_tune_est_destroy(self.h)
+            self.h = None
+
+    def _args(self, iq_ptrs, n_samples):
+        n = [int(v) for v in n_samples]
+        if len(n) != self.n or len(iq_ptrs) != self.n:
+            raise LsdrError(f"tune estimator: {len(iq_ptrs)} pointers and {len(n)} lengths for {self.n} captures")
+        return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs]), (c_sz * self.n)(*n)
+
+    def run_async(self, iq_ptrs, n_samples):
+        """Queues the estimate of every capture's first n_samples[i] items; a pointer may be None where the length is 0."""
+        check(lib.lsdr_tune_est_run_async(self.h, *self._args(iq_ptrs, n_samples)))
+
+    def wait(self):
+        check(lib.lsdr_tune_est_wait(self.h, self._out))
+        return [r.as_dict() for r in self._out]
+
+    def estimate(self, iq_ptrs, n_samples):
+        """One run, synchronously: [dict(tune, quality, bin, blocks, power [l, c, r], mean_power)] per capture."""
+        self.run_async(iq_ptrs, n_samples)
+        return self.wait()
+
+
 class _TailBatch:
     """What the objects in front of the device-resident FEC tail share (CaptureBatch, HsBatch): a batch of self.n captures through
     run_async / wait, the TS download, and fetching TS and stage bytes.  A subclass sets _what, its name in error texts, and _c, the
@@ -879,6 +941,10 @@ class _TailBatch:
         return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in ptrs])
 
     def close(self):
+        est = getattr(self, "_est", None)
+        if est:
+            est[1].close()
+            self._est = None
         if self.h:
             self._fn("destroy")(self.h)
             self.h = None
@@ -941,6 +1007,20 @@ class _TailBatch:
         """decode with a length and a tune per capture (run_each_async)."""
         self.run_each_async(iq_ptrs, n_samples, tune)
         return self._results_and_ts()
+
+    def decode_estimated(self, iq_ptrs, n_samples, blocks=8, min_quality=TUNE_MIN_QUALITY):
+        """decode_each with every capture's tune ESTIMATED from its own samples (TuneEstimator in this object's sample format, over the
+        first `blocks` blocks): (results, [TS bytes per capture], estimates).  A capture whose quality is below min_quality has no line
+        worth tuning to and is decoded with tune 0.  QPSK, |offset| < 1/8 cycle per sample."""
+        est = getattr(self, "_est", None)
+        if not est or est[0] != int(blocks):
+            if est:
+                est[1].close()
+            self._est = est = (int(blocks), TuneEstimator(self.ctx, self.n, getattr(self, "in_format", IN_CU8), getattr(self, "in_scale", 0.0), blocks))
+        estimates = est[1].estimate(iq_ptrs, n_samples)
+        tune = [e["tune"] if e["quality"] >= min_quality else 0.0 for e in estimates]
+        res, ts = self.decode_each(iq_ptrs, n_samples, tune)
+        return res, ts, estimates
 
     def stage_bytes(self, i, which, n):
         """The first n bytes in front of mpeg_sync ("deconv") or behind it ("mpeg") of capture i after a run (host)."""
