@@ -962,6 +962,57 @@ void lsdr_tune_est_destroy(lsdr_tune_est *e);
 int lsdr_tune_est_run_async(lsdr_tune_est *e, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
 int lsdr_tune_est_wait(lsdr_tune_est *e, lsdr_tune_estimate *out /* [B] */);
 
+/* ------------------------------------------------------------ resample batch: --derotate --resample for many captures
+ * The batch decoders take omega = Fs/Fm in [1, 8] and have no filter in front of the receiver; a recording from an ordinary SDR is wider
+ * (2.4 MS/s around a 250 kS/s carrier is omega 9.6).  leandvb puts rotator<f32> (--derotate, leandvb.cc:310-318, sdr.h:1226-1259) and a
+ * decimating low-pass fir_filter<cf32,float> (--resample, leandvb.cc:353-384, dsp.h:219-285) there.  This is that front end for B captures
+ * in ONE launch: any of the five sample formats in, each capture with its own length and its own carrier offset, cf32 streams out, which
+ * lsdr_capture_any_create(LSDR_IN_CF32, in_scale 1) decodes unchanged at omega / decim (the taps have DC gain 1: a capture at the level
+ * contract's RMS stays there).  The hs batch stays cu8 and is not served.
+ *
+ * THE ARITHMETIC, one float32 rounding per operation (no contraction).  For one capture of n items, N = ncoeffs, D = decim, taps h:
+ *   1 x[k] = float(item − Z)·in_scale, exactly as the capture batch's loads convert (lsdr_capture_input_cfg; a scale of 0 or 1 multiplies
+ *     by nothing);
+ *   2 ifreq = (int)(tune·65536), C truncation (rotator's own `int ifreq = freq * 65536`).  Sample k has the phase index
+ *     (−k·ifreq) mod 65536, taken into [0, 65536) with 64-bit k; (c, s) = T[index] with T[j] = ((float)cos(2πj/65536), (float)sin(2πj/65536))
+ *     evaluated in double at create — one table for all captures;  y.re = x.re·c − x.im·s;  y.im = x.re·s + x.im·c.
+ *     This is rotator<f32>(−ifreq/65536) with EXACT phases: the reference's table is cosf of an angle rounded to float, and that noise is
+ *     not reproduced (the stance lsdr_notch_fir takes).  Measured against the reference chain: tests/test_resample_abi.py, DESIGN.md §4.9;
+ *   3 out[m] = Σ_{i=0…N−1} h[i]·y[N + m·D − i], i ascending, re and im separately, each from 0 by acc = acc + h[i]·y: real taps in
+ *     fir_filter's order (dsp.h:246-262);
+ *   4 produced = n ≥ N ? min((n − N)/D, cap_out) : 0; consumed = produced·D.  Both are functions of the sizes, known at run_async: wait is
+ *     one event synchronisation, nothing is counted on the device.
+ * So: with ifreq == 0 the output equals cconverter / scaler → fir_filter in LSDR_FIR_EXACT as values (a −0 may come out as +0); and a
+ * capture's output is a pure function of its own samples, its tune and the taps — bit for bit the same alone, in any batch, in any place
+ * of it, from a 16-byte aligned pointer or an item-aligned one, and in every format that converts to the same floats.
+ * tune has lsdr_capture_each's sign (a capture multiplied by exp(+j2πfn) is given +f) and is applied as ifreq/65536; what is left,
+ * (f − ifreq/65536)·D cycles per decimated sample, is the decoder's tune (lsdr_tune_est on the decimated stream measures it).
+ * LIMITS: decim 1 … 64, ncoeffs 2 … 1024, n_captures ≤ 65535; anything else is LSDR_E_UNSUPPORTED at create.
+ * LSDR_E_ARG, with a message naming the field, the object (if any) left usable: n_captures < 1, in_format outside the five, in_scale
+ * negative or not finite, nonzero reserved (cfg or each), coeffs_host NULL; n_samples > max_samples, tune not finite or |tune| ≥ 0.5, an
+ * input pointer not aligned to its item (2, 2, 4, 4, 8 bytes), an output pointer not aligned to 16 bytes, samples without a pointer, outputs
+ * without an output pointer, cap_out smaller than some capture's (n − N)/D (refused, never truncated), run_async with a run in flight, wait
+ * with none.  n_samples < N + D is a valid capture that produces nothing; iq_dev[i] may be NULL only where n_samples is 0. */
+/* host only: leandvb.cc:353-378 for omega = Fs/Fm.  decim 0: (int)(omega/4), at least 1.  order = (int)(rej*omega/(22*0.5*rolloff))
+ * made even, Fcut = 0.5*(1+rolloff/2)/omega, filtergen::lowpass + normalize_dcgain(1) through lsdr_filtergen_*: the reference's floats.
+ * *decim_out and *ncoeffs are always written; LSDR_E_ARG where cap < *ncoeffs (or coeffs_host is NULL): nothing is written to coeffs_host. */
+int lsdr_resample_design(float omega, float rolloff, float rej, unsigned decim, unsigned *decim_out,
+                         float *coeffs_host, unsigned cap, unsigned *ncoeffs);
+typedef struct lsdr_resample_batch lsdr_resample_batch;
+typedef struct { int n_captures; size_t max_samples; int in_format; float in_scale;   /* as lsdr_capture_input_cfg */
+                 unsigned ncoeffs; const float *coeffs_host; unsigned decim; int reserved[6]; } lsdr_resample_batch_cfg;
+typedef struct { uint64_t consumed, produced; int32_t ifreq; float applied; /* ifreq/65536 */ uint32_t pad[2]; } lsdr_resample_result;
+int  lsdr_resample_batch_create(lsdr_ctx*, const lsdr_resample_batch_cfg*, lsdr_resample_batch**);
+void lsdr_resample_batch_destroy(lsdr_resample_batch*);
+/* the outputs per workgroup tile chosen for (ncoeffs, decim): the lengths at which the kernel changes its path are multiples of it */
+unsigned lsdr_resample_batch_tile(const lsdr_resample_batch*);
+/* each[i] = {n_samples, tune}: lsdr_capture_each, same sign (a capture multiplied by exp(+j2πfn) is given +f).
+ * out_dev: HOST array of B DEVICE pointers, 16-byte aligned, cap_out cf32 items each (may be NULL where the capture produces nothing).
+ * Queues one launch over all captures on the context's stream and returns; one run in flight per object. */
+int  lsdr_resample_batch_run_async(lsdr_resample_batch*, const void *const *iq_dev, const lsdr_capture_each *each,
+                                   lsdr_cf32 *const *out_dev, size_t cap_out);
+int  lsdr_resample_batch_wait(lsdr_resample_batch*, lsdr_resample_result *results /* [B], may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

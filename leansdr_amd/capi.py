@@ -393,6 +393,24 @@ _sig("lsdr_tune_est_destroy", None, [vp])
 _sig("lsdr_tune_est_run_async", C.c_int, [vp, vp, psz])
 _sig("lsdr_tune_est_wait", C.c_int, [vp, C.POINTER(TuneEstimate)])
 
+
+class ResampleBatchCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("max_samples", C.c_size_t), ("in_format", C.c_int), ("in_scale", C.c_float), ("ncoeffs", C.c_uint),
+                ("coeffs_host", vp), ("decim", C.c_uint), ("reserved", C.c_int * 6)]
+
+
+class ResampleResult(C.Structure):
+    """lsdr_resample_result: what one capture consumed and produced, and the derotation it got (ifreq / 65536 cycles per sample)."""
+    _fields_ = [("consumed", C.c_uint64), ("produced", C.c_uint64), ("ifreq", C.c_int32), ("applied", C.c_float), ("pad", C.c_uint32 * 2)]
+
+
+_sig("lsdr_resample_design", C.c_int, [c_f, c_f, c_f, C.c_uint, C.POINTER(C.c_uint), vp, C.c_uint, C.POINTER(C.c_uint)])
+_sig("lsdr_resample_batch_create", C.c_int, [vp, C.POINTER(ResampleBatchCfg), C.POINTER(vp)])
+_sig("lsdr_resample_batch_destroy", None, [vp])
+_sig("lsdr_resample_batch_tile", C.c_uint, [vp])
+_sig("lsdr_resample_batch_run_async", C.c_int, [vp, vp, C.POINTER(CaptureEach), vp, c_sz])
+_sig("lsdr_resample_batch_wait", C.c_int, [vp, C.POINTER(ResampleResult)])
+
 #: decode_estimated's default threshold on `quality`: the geometric mean of what Gaussian noise alone reaches (3.1) and the weakest of the
 #: test captures (347), rounded (DESIGN.md §4.8)
 TUNE_MIN_QUALITY = 30.0
@@ -1153,6 +1171,146 @@ class HsBatch(_TailBatch):
     def symbols(self, i, n):
         """The first n hard symbols of capture i after a run (host)."""
         return self._fetch(self.symbols_ptr(i), n)
+
+
+def resample_design(omega, rolloff=0.35, rej=10.0, decim=0):
+    """leandvb's --resample filter for omega = Fs/Fm (lsdr_resample_design, leandvb.cc:353-378): (decim, coeffs).  decim 0: (int)(omega/4),
+    at least 1."""
+    d, n = C.c_uint(), C.c_uint()
+    lib.lsdr_resample_design(omega, rolloff, rej, int(decim), C.byref(d), None, 0, C.byref(n))       # the size first
+    if not n.value:
+        raise LsdrError(f"lsdr error: {lib.lsdr_last_error().decode()}")
+    out = np.empty(n.value, np.float32)
+    check(lib.lsdr_resample_design(omega, rolloff, rej, int(decim), C.byref(d), _np(out), len(out), C.byref(n)))
+    return d.value, out[:n.value]
+
+
+class ResampleBatch:
+    """lsdr_resample_batch: leandvb's --derotate --resample for n_captures captures in one launch — each capture of in_format items, with
+    its own length and carrier offset, converted, derotated by (int)(tune·65536)/65536 cycles per sample, low-passed by the real taps
+    `coeffs` and decimated by `decim` into a cf32 stream (what CaptureBatch(in_format=IN_CF32, in_scale=1) decodes)."""
+
+    def __init__(self, ctx, n_captures, max_samples, coeffs, decim, in_format=IN_CU8, in_scale=0.0):
+        self.ctx, self.n, self.h = ctx, int(n_captures), None
+        self.coeffs = np.ascontiguousarray(coeffs, np.float32)
+        self.decim = int(decim)
+        cfg = ResampleBatchCfg()
+        cfg.n_captures, cfg.max_samples, cfg.in_format, cfg.in_scale = self.n, int(max_samples), int(in_format), float(in_scale)
+        cfg.ncoeffs, cfg.coeffs_host, cfg.decim = len(self.coeffs), self.coeffs.ctypes.data, self.decim
+        h = vp()
+        check(lib.lsdr_resample_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.tile = lib.lsdr_resample_batch_tile(h)
+        self._res = (ResampleResult * max(self.n, 1))()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_resample_batch_destroy(self.h)
+            self.h = None
+
+    def produced(self, n_samples):
+        """What a capture of n_samples items produces: (n − N) // D, 0 below N."""
+        return max(0, int(n_samples) - len(self.coeffs)) // self.decim
+
+    def _args(self, ptrs, lengths, tune, outs):
+        n = [int(v) for v in lengths]
+        t = [float(tune)] * self.n if np.isscalar(tune) else [float(v) for v in tune]
+        if not (len(n) == len(t) == len(ptrs) == len(outs) == self.n):
+            raise LsdrError(f"resample batch: {len(ptrs)} pointers, {len(n)} lengths, {len(t)} tunes and {len(outs)} outputs for {self.n} captures")
+        e = (CaptureEach * max(self.n, 1))()
+        for i in range(self.n):
+            e[i].n_samples, e[i].tune = n[i], t[i]
+        as_vp = lambda ps: (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in ps])
+        return as_vp(ptrs), e, as_vp(outs)
+
+    def run_async(self, ptrs, lengths, tune, outs, cap_out):
+        """Queues the run: ptrs / outs device pointers per capture (None where there are no samples / no outputs), lengths in items, tune
+        in cycles per sample (a scalar or one per capture), cap_out cf32 items of room behind every output pointer."""
+        p, e, o = self._args(ptrs, lengths, tune, outs)
+        check(lib.lsdr_resample_batch_run_async(self.h, p, e, o, int(cap_out)))
+
+    def wait(self):
+        """[dict(consumed, produced, ifreq, applied)] per capture."""
+        check(lib.lsdr_resample_batch_wait(self.h, self._res))
+        return [dict(consumed=int(r.consumed), produced=int(r.produced), ifreq=int(r.ifreq), applied=float(r.applied)) for r in self._res[:self.n]]
+
+    def run(self, ptrs, lengths, tune, outs, cap_out):
+        self.run_async(ptrs, lengths, tune, outs, cap_out)
+        return self.wait()
+
+
+class ResampledDecoder:
+    """Oversampled captures (omega = Fs/Fm above the batch decoders' 8) from their raw samples to TS: estimate every capture's carrier
+    offset (TuneEstimator on the raw samples), derotate + low-pass + decimate (ResampleBatch, leandvb's --derotate --resample with
+    resample_design's filter), estimate what is left on the decimated streams (TuneEstimator(IN_CF32)), decode them
+    (CaptureBatch(in_format=IN_CF32, in_scale=1) at omega / decim with the fine estimates as per-capture tunes).  QPSK; |offset| < 1/8 cycle
+    per raw sample where it is estimated.  The converted samples must meet the level contract (RMS near 75): the taps have DC gain 1.
+    The decoder's tiles default to 896 symbols of warm-up and eight times that per tile (tile_warmup= / tile_len= in decimated samples
+    override them): the capture batch's own defaults count samples and are too short at omega 4 … 8.
+    anf=1 runs the decoder's notch on the DECIMATED stream, where leandvb's auto_notch sees the raw one (it sits in front of the
+    rotator): interferers the low-pass removed are not there to be found, and the notch's bins are those of the decimated rate."""
+
+    def __init__(self, ctx, n_captures, max_samples, omega, in_format=IN_CU8, in_scale=0.0, fec=FEC12, viterbi=None, anf=0, blocks=8,
+                 rolloff=0.35, rej=10.0, decim=0, **batch_kw):
+        self.ctx, self.n, self.max_samples = ctx, int(n_captures), int(max_samples)
+        self.decim, self.coeffs = resample_design(omega, rolloff, rej, decim)
+        self.omega_out = float(omega) / self.decim
+        self.cap_out = max(1, (self.max_samples - len(self.coeffs)) // self.decim)
+        # the decoder's tiles: 896 symbols of warm-up, tiles eight times that.  The capture batch's default of 512 samples is 64 … 128
+        # symbols at omega_out 4 … 8 and leaves seams unreconciled there (DESIGN.md §4.9 has the measurements)
+        warm = -(-int(896 * self.omega_out) // 128) * 128
+        batch_kw.setdefault("tile_warmup", warm)
+        batch_kw.setdefault("tile_len", -(-8 * batch_kw["tile_warmup"] // 2048) * 2048)
+        self._parts, self._outs = [], []
+        try:
+            self.est_raw = self._own(TuneEstimator(ctx, self.n, in_format, in_scale, blocks))
+            self.resampler = self._own(ResampleBatch(ctx, self.n, self.max_samples, self.coeffs, self.decim, in_format, in_scale))
+            self.est_fine = self._own(TuneEstimator(ctx, self.n, IN_CF32, 1.0, blocks))
+            self.batch = self._own(CaptureBatch(ctx, self.n, self.cap_out, self.omega_out, fec=fec, anf=anf, viterbi=viterbi, in_format=IN_CF32,
+                                                in_scale=1.0, **batch_kw))
+            self._outs = [ctx.alloc(self.cap_out * 8) for _ in range(self.n)]
+        except Exception:
+            self.close()
+            raise
+
+    def _own(self, part):
+        self._parts.append(part)
+        return part
+
+    def close(self):
+        for p in reversed(self._parts):
+            p.close()
+        for b in self._outs:
+            b.free()
+        self._parts, self._outs = [], []
+
+    def outputs(self, i, n):
+        """The first n items of capture i's decimated stream after a decode (host, complex64)."""
+        return self.ctx.download(self._outs[i], np.complex64, int(n))
+
+    def decode(self, ptrs, lengths, tune=None, fine=True, min_quality=TUNE_MIN_QUALITY):
+        """(results, [TS bytes per capture], info).  tune: None = estimated from the raw samples (0 where the quality is below min_quality),
+        else cycles per raw sample, a scalar or one per capture.  fine=False, or a fine quality below min_quality: the decoder's tune is what
+        the derotation left by construction, (tune − ifreq/65536)·decim.  info[i] = dict(raw: the raw estimate or None, tune_raw, ifreq,
+        applied, fine: the fine estimate or None, tune: the decoder's, produced)."""
+        raw = [None] * self.n
+        if tune is None:
+            raw = self.est_raw.estimate(ptrs, lengths)
+            t_raw = [e["tune"] if e["quality"] >= min_quality else 0.0 for e in raw]
+        else:
+            t_raw = [float(tune)] * self.n if np.isscalar(tune) else [float(v) for v in tune]
+        outs = [b.ptr for b in self._outs]
+        rs = self.resampler.run(ptrs, lengths, t_raw, outs, self.cap_out)
+        produced = [r["produced"] for r in rs]
+        t_dec = [(t - r["applied"]) * self.decim for t, r in zip(t_raw, rs)]
+        est = [None] * self.n
+        if fine:
+            est = self.est_fine.estimate(outs, produced)
+            t_dec = [e["tune"] if e["quality"] >= min_quality else t for e, t in zip(est, t_dec)]
+        res, ts = self.batch.decode_each(outs, produced, t_dec)
+        info = [dict(raw=raw[i], tune_raw=t_raw[i], ifreq=rs[i]["ifreq"], applied=rs[i]["applied"], fine=est[i], tune=t_dec[i], produced=produced[i])
+                for i in range(self.n)]
+        return res, ts, info
 
 
 def hs2_pack(symbols, offset=0):
