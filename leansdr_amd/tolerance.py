@@ -17,12 +17,22 @@ QPSK stream at the bench condition (Es/N0 = 20 dB in leansdr_amd.synth's definit
 
 LOW_SNR holds the same bounds for the 10–12 dB checks (the loops' own noise is larger there; a few seams may stay
 unrepaired — they cost a handful of symbols that the FEC corrects, and are counted).
+
+Which constellations: the tolerance is stated and tested for BPSK (TOL_BPSK), QPSK (TOL, LOW_SNR) and 8PSK (TOL_PSK8) —
+tests/test_gpu_rx_tiled_constellations.py, on streams whose carrier phase walks through every rotation of the constellation.
+For 16-ary and denser constellations the per-tile re-acquisition from phase = 0 is not reliable even with the reference's own
+arithmetic: restated with the serial oracle alone (tests/test_oracle_rx_tile_emulation.py;
+profiles/rx_tiled_constellations/emulation.txt), 1024-sample tiles after 1024 samples of warm-up at 26 dB give 99.45 % of the
+serial receiver's decisions for 16QAM 3/4 and 92.4 % for 16APSK 3/4 (3 of 22 tiles below 95 %, the worst at 33 %: the 12-point
+ring false-locks).  Nothing is refused, but those constellations should use the serial mode.
 """
 import os
 
 import numpy as np
 
 COST_MAX = 11236          # largest |cost| of the QPSK table (cstln_lut<256>, sdr.h:529-560)
+COST_MAX_BPSK = 31799     # largest |cost| of the BPSK 1/2 table
+COST_MAX_PSK8 = 7943      # largest |cost| of the 8PSK 2/3 table
 
 # How the bounds were set (round 4): every comparison made by the gpu tests and by bench.py's verification was logged
 # (LSDR_TOL_LOG, below; profiles/r04_tolerance.txt) and each bound is 1.5 × the largest figure seen, rounded up —
@@ -54,6 +64,19 @@ COST_MAX = 11236          # largest |cost| of the QPSK table (cstln_lut<256>, sd
 # The default engine stays inside freq_atol tuned or not (at most 9.08e-6), so TOL has no tuned entry.  The Viterbi engine at noise 18 holds
 # 6.84e-6 untuned and 3.55e-5 at a tune of −1e-3 — a single instant; the means agree to 2e-6 and the serial FREQ jitters more than that
 # between instants.  SS and MER stay far inside their bounds tuned as well (0.9 %, 0.21 dB).
+#
+# TOL_BPSK / TOL_PSK8 (the tiled mode beyond QPSK): NOT from the GPU's output but from the tile algorithm restated with the serial oracle alone
+# (tests/rx_tiled_common.emulate_tiles: every tile restarts the reference's loops from mu = phase = 0 one warm-up early; figures against the
+# serial oracle in profiles/rx_tiled_constellations/emulation.txt, written by tests/test_oracle_rx_tile_emulation.py, which also asserts that the
+# bounds below follow from them).  Streams of tests/rx_tiled_common.CASES, geometries (1024, 1024) / (512, 512) / (256, 1024); each bound is
+# 1.5 × the worst of the three, rounded up —
+#   TOL_BPSK  BPSK 1/2 at 12 dB: mean |Δcost| 876 / 978 / 908, p99 2215 / 2544 / 2332, max 8766 / 9047 / 8783 (|cost| <= COST_MAX_BPSK),
+#             identical decisions 1 / 0.999866 / 0.999955
+#   TOL_PSK8  8PSK 2/3 at 26 dB: mean 70 / 122 / 84, p99 236 / 367 / 265, max 536 / 618 / 428 (|cost| <= COST_MAX_PSK8),
+#             identical decisions 0.999950 / 0.999749 / 1
+# The QPSK stream of those tests (table slicer; carrier offset with allow_drift) runs under TOL itself: emulated mean 71 / 115 / 73, p99 212 / 424 /
+# 212, max 424 / 1484 (2544 with the offset) / 424, every decision identical.  SS, MER and the seams are held to TOL's entries as they stand
+# (the wrong estimator branch for BPSK would move MER by about 3 dB); freq_atol is carried over unmeasured: the capture batch decodes QPSK only.
 TOL = dict(
     min_equal_decisions=0.9995,
     max_mean_abs_dcost=330,       # 1.5 × 219
@@ -76,6 +99,22 @@ LOW_SNR = dict(
     freq_atol=3e-5,               # 1.5 × 1.97e-5: the capture batch's FREQ reports, Viterbi engine at noise 18 (see above)
     freq_atol_tuned=5.33e-5,      # 1.5 × 3.55e-5: … of a tuned capture (see above)
 )
+
+TOL_BPSK = dict(TOL,
+    min_equal_decisions=0.99979,  # 1 − 1.5 × (1 − 0.999866)
+    max_mean_abs_dcost=1470,      # 1.5 × 978.4
+    max_p99_abs_dcost=3820,       # 1.5 × 2544
+    max_abs_dcost=13600,          # 1.5 × 9047
+)
+
+TOL_PSK8 = dict(TOL,
+    min_equal_decisions=0.99962,  # 1 − 1.5 × (1 − 0.999749)
+    max_mean_abs_dcost=185,       # 1.5 × 121.7
+    max_p99_abs_dcost=555,        # 1.5 × 367.3
+    max_abs_dcost=930,            # 1.5 × 618
+)
+
+_TOL_NAMES = ((TOL, "TOL"), (TOL_BPSK, "TOL_BPSK"), (TOL_PSK8, "TOL_PSK8"))
 
 
 def check_tiled(sym, ref_sym, stats=None, first_exact=0, tol=None):
@@ -107,5 +146,5 @@ def check_tiled(sym, ref_sym, stats=None, first_exact=0, tol=None):
     if log:
         import json
         with open(log, "a") as f:
-            f.write(json.dumps(dict(rep, tol="TOL" if tol is TOL else "LOW_SNR", where=os.environ.get("PYTEST_CURRENT_TEST", ""))) + "\n")
+            f.write(json.dumps(dict(rep, tol=next((n for t, n in _TOL_NAMES if tol is t), "LOW_SNR"), where=os.environ.get("PYTEST_CURRENT_TEST", ""))) + "\n")
     return rep
