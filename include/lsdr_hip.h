@@ -1017,6 +1017,79 @@ int  lsdr_resample_batch_run_async(lsdr_resample_batch*, const void *const *iq_d
                                    lsdr_cf32 *const *out_dev, size_t cap_out);
 int  lsdr_resample_batch_wait(lsdr_resample_batch*, lsdr_resample_result *results /* [B], may be NULL */);
 
+/* ------------------------------------------------------------ spectrum batch: --cnr and --fd-spectrum for many captures
+ * cnr_fft<f32> (sdr.h:1273-1345, leandvb --cnr) and spectrum<f32> (sdr.h:1347-1404, --fd-spectrum) for B captures in shared launches: any
+ * of the five sample formats in, each capture with its own length and its own band centre.  One object serves both blocks; they differ in
+ * nfft, kavg and what they emit.  It reads the raw capture, needs no lock and touches no decode kernel.  The single-stream objects
+ * (lsdr_cnr_fft_*, lsdr_spectrum_*) stay what they are; a capture's results here are theirs bit for bit.
+ *
+ * THE CONTRACT: whole blocks of nfft samples only; decimation >= nfft (at most one row per block; == nfft is every block, a dense
+ * waterfall); bandwidth <= 0.25; the centre is GIVEN by the caller (each[i].tune, cycles per sample: what *freq_tap·tap_multiplier is in
+ * the reference — the array passed to lsdr_capture_each_run_async can be passed here unchanged); libm (logf, log10f) runs on the host.
+ *
+ * THE ARITHMETIC, one float32 rounding per operation (no contraction), for one capture of n items:
+ *   1 J = n / nfft whole blocks; block j is the nfft samples at j·nfft.  run()'s phase counter adds nfft per block and fetches the block
+ *     with which it reaches `decimation`: row m (1-based) is taken from block ceil(m·decimation/nfft) − 1, and there are
+ *     floor(J·nfft/decimation) rows; consumed = J·nfft.  Both are functions of the sizes, known at run_async;
+ *   2 x[k] = float(item − Z)·in_scale, exactly as the capture batch's loads convert (lsdr_capture_input_cfg);
+ *   3 X = cfft_engine<float>::inplace(x, true): radix-2, the reference's butterfly (dsp.h:96-104) evaluated once per butterfly, with the
+ *     host-built cosf/sinf table and the 1/n of the reverse direction — lsdr_cfft_dev's bits;
+ *   4 power = re·re + im·im;  the first row sets avgpower = power and THEN, like every row, avgpower = avgpower·(1 − kavg) + power·kavg
+ *     (sdr.h:1313-1320);
+ *   5 bandwidth > 0: icf = floor(center·nfft + 0.5), bwslots = (int)((bandwidth/4)·nfft); the three avgslots sums (icf ± bwslots,
+ *     icf − 4·bwslots … icf − 3·bwslots, icf + 3·bwslots … icf + 4·bwslots) are serial float sums in index order, indices & (nfft − 1)
+ *     (sdr.h:1334-1338); the host then forms c2plusn2, n2, c2 and 10·logf(c2/n2)/logf(10), or −50 — one CNR value per row;
+ *   6 emit_rows: every row's avgpower is kept in device memory (linear); the rows accessor returns 10·log10f of it, the two halves
+ *     swapped as do_spectrum writes them (sdr.h:1391-1394).
+ * A capture's results are a pure function of its own samples, its length and its centre — bit for bit the same alone, in any batch, in any
+ * place of it, with any slab_rows and stages_per_pass, and in every format that converts to the same floats.  A run starts from fresh
+ * state (a newly constructed block per capture); nothing is carried from one run to the next.
+ * SLABS: the rows are worked off slab_rows at a time (three launches per slab, shared by all captures); the scratch is
+ * n_captures·slab_rows·nfft floats whatever the captures' lengths, and avgpower is carried in device memory from slab to slab.
+ * run_async queues everything on the context's stream and returns; wait is one event synchronisation.  One run in flight per object.
+ * iq_dev: HOST array of B DEVICE pointers, each aligned to its item size (2, 2, 4, 4, 8 bytes; a 16-byte aligned capture is read by
+ * 16-byte loads), NULL only where n_samples is 0.  Nothing behind a capture's last fetched block is read.
+ * LSDR_E_ARG, with a message, the object (if any) left usable: n_captures outside 1 … 65535, in_format outside the five, in_scale negative
+ * or not finite, nfft no power of two or outside 64 … 4096, decimation < nfft, bandwidth > 0.25 (cnr_fft's own message), negative or so
+ * small that (int)((bandwidth/4)·nfft) is 0, stages_per_pass > 4, nonzero reserved (cfg or each); n_samples > max_samples, a centre not
+ * finite or |centre| >= 0.5, a misaligned pointer, samples without a pointer, run_async with a run in flight, wait with none, an accessor
+ * before a finished run or for what the object was not created to produce. */
+typedef struct lsdr_spectrum_batch lsdr_spectrum_batch;
+typedef struct {
+  int n_captures;            /* B */
+  size_t max_samples;        /* the longest capture a run may bring */
+  int in_format;             /* LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32 */
+  float in_scale;            /* as lsdr_capture_input_cfg.in_scale: 0 or 1 = none */
+  int nfft;                  /* power of two, 64 … 4096 (cnr_fft: 4096, spectrum: 1024) */
+  unsigned decimation;       /* samples between fetched blocks, >= nfft */
+  float kavg;                /* 0: 0.1 */
+  float bandwidth;           /* Fm/Fs of the CNR bands, <= 0.25; 0: no CNR */
+  int emit_rows;             /* keep every row's averaged power */
+  unsigned slab_rows;        /* rows per group of launches; 0: 16 Mi floats of scratch over all captures, at most a capture's rows */
+  unsigned stages_per_pass;  /* radix-2 stages kept in registers between two LDS exchanges, 1 … 4; 0: 4.  The results do not depend on it */
+  int reserved[5];           /* 0 */
+} lsdr_spectrum_batch_cfg;   /* 72 bytes */
+typedef struct {
+  uint64_t consumed;         /* samples: the whole blocks */
+  uint64_t rows;             /* rows produced (CNR values, kept rows) */
+  int32_t icf;               /* the centre's bin, floor(center·nfft + 0.5); 0 without CNR */
+  uint32_t pad[3];
+} lsdr_spectrum_result;      /* 32 bytes */
+int  lsdr_spectrum_batch_create(lsdr_ctx*, const lsdr_spectrum_batch_cfg*, lsdr_spectrum_batch**);
+void lsdr_spectrum_batch_destroy(lsdr_spectrum_batch*);
+size_t lsdr_spectrum_batch_max_rows(const lsdr_spectrum_batch*);     /* the rows of a capture of max_samples */
+unsigned lsdr_spectrum_batch_slab_rows(const lsdr_spectrum_batch*);  /* slab_rows with the default filled in */
+/* each[i] = {n_samples, tune}: lsdr_capture_each; tune is the band centre (read with bandwidth > 0 only, checked always) */
+int  lsdr_spectrum_batch_run_async(lsdr_spectrum_batch*, const void *const *iq_dev, const lsdr_capture_each *each /* [B], host */);
+int  lsdr_spectrum_batch_wait(lsdr_spectrum_batch*, lsdr_spectrum_result *results /* [B], may be NULL */);
+/* after wait.  cnr: capture i's CNR values in dB, one per row (bandwidth > 0).  rows_db: its rows in dB, [rows][nfft], fftshifted
+ * (emit_rows; copies the rows from the device, synchronously).  *n: what was written; LSDR_E_ARG where cap is too small.
+ * rows_dev: the same rows as linear averaged power in device memory, [rows][nfft] in FFT order, valid until the next run_async; NULL
+ * without emit_rows. */
+int  lsdr_spectrum_batch_cnr(lsdr_spectrum_batch*, int i, float *cnr_out, size_t cap, size_t *n);
+int  lsdr_spectrum_batch_rows_db(lsdr_spectrum_batch*, int i, float *rows_out, size_t cap_rows, size_t *n);
+const float *lsdr_spectrum_batch_rows_dev(const lsdr_spectrum_batch*, int i);
+
 #ifdef __cplusplus
 }
 #endif

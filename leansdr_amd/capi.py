@@ -411,6 +411,28 @@ _sig("lsdr_resample_batch_tile", C.c_uint, [vp])
 _sig("lsdr_resample_batch_run_async", C.c_int, [vp, vp, C.POINTER(CaptureEach), vp, c_sz])
 _sig("lsdr_resample_batch_wait", C.c_int, [vp, C.POINTER(ResampleResult)])
 
+
+class SpectrumBatchCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("max_samples", C.c_size_t), ("in_format", C.c_int), ("in_scale", C.c_float), ("nfft", C.c_int),
+                ("decimation", C.c_uint), ("kavg", C.c_float), ("bandwidth", C.c_float), ("emit_rows", C.c_int), ("slab_rows", C.c_uint),
+                ("stages_per_pass", C.c_uint), ("reserved", C.c_int * 5)]
+
+
+class SpectrumResult(C.Structure):
+    """lsdr_spectrum_result: the whole blocks one capture consumed, its rows, and the bin of its band centre."""
+    _fields_ = [("consumed", C.c_uint64), ("rows", C.c_uint64), ("icf", C.c_int32), ("pad", C.c_uint32 * 3)]
+
+
+_sig("lsdr_spectrum_batch_create", C.c_int, [vp, C.POINTER(SpectrumBatchCfg), C.POINTER(vp)])
+_sig("lsdr_spectrum_batch_destroy", None, [vp])
+_sig("lsdr_spectrum_batch_max_rows", c_sz, [vp])
+_sig("lsdr_spectrum_batch_slab_rows", C.c_uint, [vp])
+_sig("lsdr_spectrum_batch_run_async", C.c_int, [vp, vp, C.POINTER(CaptureEach)])
+_sig("lsdr_spectrum_batch_wait", C.c_int, [vp, C.POINTER(SpectrumResult)])
+_sig("lsdr_spectrum_batch_cnr", C.c_int, [vp, C.c_int, vp, c_sz, psz])
+_sig("lsdr_spectrum_batch_rows_db", C.c_int, [vp, C.c_int, vp, c_sz, psz])
+_sig("lsdr_spectrum_batch_rows_dev", vp, [vp, C.c_int])
+
 #: decode_estimated's default threshold on `quality`: the geometric mean of what Gaussian noise alone reaches (3.1) and the weakest of the
 #: test captures (347), rounded (DESIGN.md §4.8)
 TUNE_MIN_QUALITY = 30.0
@@ -1239,6 +1261,105 @@ class ResampleBatch:
         return self.wait()
 
 
+class SpectrumBatch:
+    """lsdr_spectrum_batch: leandvb's --cnr (cnr_fft, sdr.h:1273-1345) and --fd-spectrum (spectrum, sdr.h:1347-1404) for n_captures
+    captures in shared launches — each capture of in_format items with its own length and band centre; whole blocks of nfft samples, a row
+    every `decimation` samples (>= nfft; == nfft: every block).  bandwidth > 0 (Fm/Fs, at most 0.25): one CNR value in dB per row.
+    rows=True: every row's averaged power is kept (rows_db on the host in dB, fftshifted; rows_linear_dev on the device)."""
+
+    def __init__(self, ctx, n_captures, max_samples, nfft=4096, decimation=1048576, kavg=0.1, bandwidth=0.0, rows=False, in_format=IN_CU8,
+                 in_scale=1.0, slab_rows=0, stages_per_pass=0):
+        self.ctx, self.n, self.h = ctx, int(n_captures), None
+        self.nfft, self.decimation, self.bandwidth, self.rows = int(nfft), int(decimation), float(bandwidth), bool(rows)
+        cfg = SpectrumBatchCfg()
+        cfg.n_captures, cfg.max_samples, cfg.in_format, cfg.in_scale = self.n, int(max_samples), int(in_format), float(in_scale)
+        cfg.nfft, cfg.decimation, cfg.kavg, cfg.bandwidth = self.nfft, self.decimation, float(kavg), self.bandwidth
+        cfg.emit_rows, cfg.slab_rows, cfg.stages_per_pass = int(self.rows), int(slab_rows), int(stages_per_pass)
+        h = vp()
+        check(lib.lsdr_spectrum_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.max_rows = int(lib.lsdr_spectrum_batch_max_rows(h))
+        self.slab_rows = int(lib.lsdr_spectrum_batch_slab_rows(h))
+        self._res = (SpectrumResult * max(self.n, 1))()
+
+    @classmethod
+    def cnr(cls, ctx, n_captures, max_samples, omega, Fs_over_Finfo, **kw):
+        """leandvb --cnr for omega = Fs/Fm: cnr_fft(bandwidth = Fm/Fs) with a value every decimation(Fs, 1 Hz) = (int)Fs samples
+        (leandvb.cc:327-328); Fs_over_Finfo is Fs over the 1 Hz of information rate."""
+        kw.setdefault("nfft", 4096)
+        return cls(ctx, n_captures, max_samples, decimation=max(int(Fs_over_Finfo), 1), bandwidth=1.0 / float(omega), **kw)
+
+    @classmethod
+    def spectrum(cls, ctx, n_captures, max_samples, Fs_over_Finfo, **kw):
+        """leandvb --fd-spectrum: spectrum<f32> (1024 bins) with kavg 0.5 and a row every (int)Fs samples (leandvb.cc:339-342)."""
+        kw.setdefault("kavg", 0.5)
+        return cls(ctx, n_captures, max_samples, nfft=1024, decimation=max(int(Fs_over_Finfo), 1), rows=True, **kw)
+
+    def close(self):
+        if self.h:
+            lib.lsdr_spectrum_batch_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _args(self, ptrs, lengths, center):
+        n = [int(v) for v in lengths]
+        t = [0.0 if center is None else float(center)] * self.n if center is None or np.isscalar(center) else [float(v) for v in center]
+        if not (len(n) == len(t) == len(ptrs) == self.n):
+            raise LsdrError(f"spectrum batch: {len(ptrs)} pointers, {len(n)} lengths and {len(t)} centres for {self.n} captures")
+        e = (CaptureEach * max(self.n, 1))()
+        for i in range(self.n):
+            e[i].n_samples, e[i].tune = n[i], t[i]
+        return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in ptrs]), e
+
+    def run_async(self, ptrs, lengths, center=None):
+        """Queues the run: device pointers per capture (None where there are no samples), lengths in items, center the band centre in
+        cycles per sample (a scalar or one per capture; None: 0)."""
+        check(lib.lsdr_spectrum_batch_run_async(self.h, *self._args(ptrs, lengths, center)))
+
+    def wait(self):
+        """[dict(consumed, rows, icf)] per capture."""
+        check(lib.lsdr_spectrum_batch_wait(self.h, self._res))
+        return [dict(consumed=int(r.consumed), rows=int(r.rows), icf=int(r.icf)) for r in self._res[:self.n]]
+
+    def cnr_db(self, i):
+        """Capture i's CNR values in dB, one per row (float32)."""
+        out, n = np.empty(max(int(self._res[i].rows), 1), np.float32), c_sz()
+        check(lib.lsdr_spectrum_batch_cnr(self.h, int(i), _np(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def rows_db(self, i):
+        """Capture i's rows in dB as spectrum<f32> writes them (float32 [rows, nfft])."""
+        out, n = np.empty((max(int(self._res[i].rows), 1), self.nfft), np.float32), c_sz()
+        check(lib.lsdr_spectrum_batch_rows_db(self.h, int(i), _np(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def rows_linear_dev(self, i):
+        """Device pointer of capture i's rows as linear averaged power, [rows, nfft] float32 in FFT order (None without rows=True)."""
+        return lib.lsdr_spectrum_batch_rows_dev(self.h, int(i))
+
+    def rows_linear(self, i):
+        """rows_linear_dev(i)'s rows of the last run on the host (float32 [rows, nfft])."""
+        out = np.empty((int(self._res[i].rows), self.nfft), np.float32)
+        if out.size:
+            check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(out), vp(self.rows_linear_dev(i)), out.nbytes))
+            self.ctx.sync()
+        return out
+
+    def run(self, ptrs, lengths, center=None):
+        """One run, synchronously: per capture dict(consumed, rows, icf, cnr: float32[rows] (empty without bandwidth), rows_db: float32[rows, nfft] | None)."""
+        self.run_async(ptrs, lengths, center)
+        res = self.wait()
+        for i, r in enumerate(res):
+            r["cnr"] = self.cnr_db(i) if self.bandwidth > 0 else np.empty(0, np.float32)
+            r["rows_db"] = self.rows_db(i) if self.rows else None
+        return res
+
+
 class ResampledDecoder:
     """Oversampled captures (omega = Fs/Fm above the batch decoders' 8) from their raw samples to TS: estimate every capture's carrier
     offset (TuneEstimator on the raw samples), derotate + low-pass + decimate (ResampleBatch, leandvb's --derotate --resample with
@@ -1251,8 +1372,9 @@ class ResampledDecoder:
     rotator): interferers the low-pass removed are not there to be found, and the notch's bins are those of the decimated rate."""
 
     def __init__(self, ctx, n_captures, max_samples, omega, in_format=IN_CU8, in_scale=0.0, fec=FEC12, viterbi=None, anf=0, blocks=8,
-                 rolloff=0.35, rej=10.0, decim=0, **batch_kw):
+                 rolloff=0.35, rej=10.0, decim=0, cnr_decimation=8 * 4096, **batch_kw):
         self.ctx, self.n, self.max_samples = ctx, int(n_captures), int(max_samples)
+        self.in_format, self.cnr_decimation, self.measure = in_format, int(cnr_decimation), None
         self.decim, self.coeffs = resample_design(omega, rolloff, rej, decim)
         self.omega_out = float(omega) / self.decim
         self.cap_out = max(1, (self.max_samples - len(self.coeffs)) // self.decim)
@@ -1282,17 +1404,20 @@ class ResampledDecoder:
             p.close()
         for b in self._outs:
             b.free()
-        self._parts, self._outs = [], []
+        self._parts, self._outs, self.measure = [], [], None
 
     def outputs(self, i, n):
         """The first n items of capture i's decimated stream after a decode (host, complex64)."""
         return self.ctx.download(self._outs[i], np.complex64, int(n))
 
-    def decode(self, ptrs, lengths, tune=None, fine=True, min_quality=TUNE_MIN_QUALITY):
+    def decode(self, ptrs, lengths, tune=None, fine=True, min_quality=TUNE_MIN_QUALITY, cnr=False):
         """(results, [TS bytes per capture], info).  tune: None = estimated from the raw samples (0 where the quality is below min_quality),
         else cycles per raw sample, a scalar or one per capture.  fine=False, or a fine quality below min_quality: the decoder's tune is what
         the derotation left by construction, (tune − ifreq/65536)·decim.  info[i] = dict(raw: the raw estimate or None, tune_raw, ifreq,
-        applied, fine: the fine estimate or None, tune: the decoder's, produced)."""
+        applied, fine: the fine estimate or None, tune: the decoder's, produced).
+        cnr=True: the decimated streams are measured as well, in front of the decode and apart from it — SpectrumBatch, cnr_fft with
+        bandwidth decim/omega around the decoder's tune, a value every cnr_decimation decimated samples; info[i] gains cnr (float32, dB,
+        one value per row) and cnr_center.  It needs omega / decim >= 4 (cnr_fft's own limit)."""
         raw = [None] * self.n
         if tune is None:
             raw = self.est_raw.estimate(ptrs, lengths)
@@ -1307,9 +1432,18 @@ class ResampledDecoder:
         if fine:
             est = self.est_fine.estimate(outs, produced)
             t_dec = [e["tune"] if e["quality"] >= min_quality else t for e, t in zip(est, t_dec)]
+        measured = None
+        if cnr:
+            if self.measure is None:
+                self.measure = self._own(SpectrumBatch(self.ctx, self.n, self.cap_out, nfft=4096, decimation=self.cnr_decimation,
+                                                       bandwidth=1.0 / self.omega_out, in_format=IN_CF32, in_scale=1.0))
+            measured = self.measure.run(outs, produced, t_dec)
         res, ts = self.batch.decode_each(outs, produced, t_dec)
         info = [dict(raw=raw[i], tune_raw=t_raw[i], ifreq=rs[i]["ifreq"], applied=rs[i]["applied"], fine=est[i], tune=t_dec[i], produced=produced[i])
                 for i in range(self.n)]
+        if measured is not None:
+            for i in range(self.n):
+                info[i]["cnr"], info[i]["cnr_center"] = measured[i]["cnr"], t_dec[i]
         return res, ts, info
 
 
