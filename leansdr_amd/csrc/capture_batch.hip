@@ -15,7 +15,7 @@
 //
 // Signal reports (lsdr_capture_reports_set / _get): leandvb's --fd-info per capture — FREQ, SS, MER once per meas_decimation samples
 // (sdr.h:857-913).  The front end records and scans the estimators in its own launches (rxb_device.h); here only the libm scalars.
-#include "lsdr_internal.h"
+#include "capture_input.h"
 
 struct lsdr_capture_batch {
   lsdr_ctx *ctx;                   // the context the front end's tiles run on: the caller's, or (aux_cus) an own one on the tile partition
@@ -31,6 +31,7 @@ struct lsdr_capture_batch {
   size_t soft_cap, byte_cap;
   std::vector<lsdr_capture_viterbi_stats> vstats;
   int in_format; float in_scale;   // lsdr_capture_input_cfg (cu8, 0 by default)
+  lsdr_in_desc in;                 // … and what they come to
 };
 
 // one more round of the Viterbi stage: stream i continues behind what it has committed.  first: the symbol counts are still on the device.
@@ -81,15 +82,7 @@ static int capture_batch_partition(lsdr_capture_batch *b, lsdr_ctx *caller) {
 }
 
 static int capture_batch_build(lsdr_capture_batch *b, const lsdr_capture_viterbi_cfg *vcfg) {
-  {
-    // the input format is refused before anything is allocated (lsdr_rxb_create_in repeats the checks with their messages)
-    const int f = b->in_format;
-    LSDR_ARG(f == LSDR_IN_CU8 || f == LSDR_IN_CS8 || f == LSDR_IN_CU16 || f == LSDR_IN_CS16 || f == LSDR_IN_CF32);
-    LSDR_ARG(b->in_scale >= 0.f && !std::isinf(b->in_scale));
-    if (f == LSDR_IN_CU8 && b->in_scale != 0.f && b->in_scale != 1.0f) {
-      lsdr_set_error("capture_batch: cu8 captures take no in_scale (got %g): the cu8 kernels have no scaler", (double)b->in_scale); return LSDR_E_UNSUPPORTED;
-    }
-  }
+  LSDR_TRY(lsdr_rxb_describe_in(b->in_format, b->in_scale, &b->in));     // (refused before anything is allocated)
   LSDR_HIP(hipSetDevice(b->ctx->device));
   lsdr_ctx *const caller = b->ctx;
   int vrate = b->cfg.fec;
@@ -190,13 +183,10 @@ int lsdr_capture_any_run_async(lsdr_capture_batch *b, const void *const *iq_dev,
 int lsdr_capture_each_run_async(lsdr_capture_batch *b, const void *const *iq_dev, const lsdr_capture_each *each) {
   LSDR_ARG(b && iq_dev && each);
   const int B = b->cfg.n_captures;
+  LSDR_TRY(lsdr_in_check_each("capture_batch", "tune", (unsigned)B, iq_dev, each, nullptr, nullptr, b->cfg.max_samples, b->in.item_bytes));
   std::vector<size_t> n(B);
   std::vector<float> tune(B);
-  for (int i = 0; i < B; ++i) {
-    for (int q = 0; q < 5; ++q)
-      if (each[i].reserved[q]) { lsdr_set_error("capture_batch: capture %d: lsdr_capture_each.reserved must be 0", i); return LSDR_E_ARG; }
-    n[i] = each[i].n_samples; tune[i] = each[i].tune;
-  }
+  for (int i = 0; i < B; ++i) { n[i] = each[i].n_samples; tune[i] = each[i].tune; }
   return capture_batch_run(b, iq_dev, n.data(), tune.data());
 }
 

@@ -26,7 +26,7 @@
 // {cost, symbol, 0, phase_error, point.re, point.im} so one gather serves the
 // slicer, the PLL and the timing detector.
 #include <cmath>
-#include "lsdr_internal.h"
+#include "capture_input.h"    // (the capture batch's host side, rxb_host.h)
 
 namespace {
 

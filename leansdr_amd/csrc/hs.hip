@@ -15,7 +15,7 @@
 //                                            (hsb_device.h / hsb_host.h; the FEC tail is fec.hip's lsdr_tail)
 //
 // Tables are built on the host with the reference's libm expressions (host_tables.cpp) and uploaded once.
-#include "lsdr_internal.h"
+#include "capture_input.h"   // (lsdr_hs_batch's per-capture checks, hsb_host.h)
 
 namespace {
 

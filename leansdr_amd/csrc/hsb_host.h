@@ -183,10 +183,8 @@ int lsdr_hs_batch_create(lsdr_ctx *c, const lsdr_hs_batch_cfg *cfg, lsdr_hs_batc
 // one batch, capture i over its first n_samples[i] items with set_freq(tune[i]): what both run_async entry points come to
 static int hsb_run(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, const size_t *n_samples, const float *tune) {
   const unsigned B = (unsigned)b->cfg.n_captures;
-  for (unsigned i = 0; i < B; ++i) {
-    if (n_samples[i] > b->cfg.max_samples) { lsdr_set_error("hs_batch: capture %u has %zu samples, created for %zu", i, n_samples[i], b->cfg.max_samples); return LSDR_E_ARG; }
-    if (!iq_dev[i] && n_samples[i]) { lsdr_set_error("hs_batch: capture %u has no samples pointer", i); return LSDR_E_ARG; }
-  }
+  // (cu8: items of 2 bytes; the tune is the object's own where it is not lsdr_hs_each_run_async's, which has checked it)
+  LSDR_TRY(lsdr_in_check_each("hs_batch", "tune", B, reinterpret_cast<const void *const *>(iq_dev), nullptr, n_samples, nullptr, b->cfg.max_samples, 2));
   if (b->in_flight) { lsdr_set_error("hs_batch: a batch is in flight (lsdr_hs_batch_wait first)"); return LSDR_E_ARG; }
   lsdr_ctx *c = b->ctx;
   LSDR_HIP(hipSetDevice(c->device));
@@ -241,14 +239,10 @@ int lsdr_hs_batch_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, siz
 int lsdr_hs_each_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, const lsdr_capture_each *each) {
   LSDR_ARG(b && iq_dev && each);
   const int B = b->cfg.n_captures;
+  LSDR_TRY(lsdr_in_check_each("hs_batch", "tune", (unsigned)B, reinterpret_cast<const void *const *>(iq_dev), each, nullptr, nullptr, b->cfg.max_samples, 2));
   std::vector<size_t> n(B);
   std::vector<float> tune(B);
-  for (int i = 0; i < B; ++i) {
-    for (int q = 0; q < 5; ++q)
-      if (each[i].reserved[q]) { lsdr_set_error("hs_batch: capture %d: lsdr_capture_each.reserved must be 0", i); return LSDR_E_ARG; }
-    if (!std::isfinite(each[i].tune) || !(fabsf(each[i].tune) < 0.5f)) { lsdr_set_error("hs_batch: capture %d: tune must be finite and inside (-0.5, 0.5) cycles per sample", i); return LSDR_E_ARG; }
-    n[i] = each[i].n_samples; tune[i] = each[i].tune;
-  }
+  for (int i = 0; i < B; ++i) { n[i] = each[i].n_samples; tune[i] = each[i].tune; }
   return hsb_run(b, iq_dev, n.data(), tune.data());
 }
 

@@ -92,6 +92,8 @@ int lsdr_fir_stream_iv_launch(lsdr_ctx *c, const void *in, size_t n_in, lsdr_cf3
 // ---- capture batch (capture_batch.hip): its two halves
 // cstln_receiver.hip (rxb_host.h): the front end — auto_notch + cstln_receiver of every capture in shared launches, packed decisions out
 struct lsdr_rxb;
+struct lsdr_in_desc;                                                      // capture_input.h
+int lsdr_rxb_describe_in(int in_format, float in_scale, lsdr_in_desc *out);   // what lsdr_rxb_create_in makes of them, or its refusal
 int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, int in_format, float in_scale, lsdr_rxb **out);
 void lsdr_rxb_destroy(lsdr_rxb *b);
 int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, const size_t *n_samples /* [n] */, const float *tune /* [n] */, size_t *consumed /* [n] */,

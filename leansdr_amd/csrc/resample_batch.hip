@@ -17,8 +17,7 @@
 // out[produced − 1] is written.  All indexing of a capture is 64-bit; tile-local indices are below 2^17.  No atomics, no order that depends
 // on scheduling: a capture's output is a pure function of its samples, its tune and the taps.
 #include <cmath>
-#include "lsdr_internal.h"
-#include "tune_est_device.h"   // the formats' conversion: te_load / te_unpack = float(item − Z)·in_scale, as the capture batch's loads
+#include "capture_input.h"     // the formats' conversion: in_load / in_unpack = float(item − Z)·in_scale, as the capture batch's loads
 
 namespace {
 
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(kRsThreads) void k_resample(rs_args A) {
   const unsigned long long rem = cap.produced - m0;
   const unsigned mv = rem < A.M ? (unsigned)rem : A.M;
   const unsigned N = A.N, D = A.D, l = threadIdx.x;
-  constexpr unsigned kB = te_item<K>::kBytes, kPer = 16u / kB;
+  constexpr unsigned kB = in_item<K>::kBytes, kPer = 16u / kB;
   const float sc = A.in_scale; const unsigned flip = A.in_flip;
 
   // ---- stage: tile-local t ∈ [0, T) ↔ sample j = j0 + t; the last one is N + (m0 + mv − 1)·D ≤ n − 1
@@ -93,12 +92,12 @@ __global__ __launch_bounds__(kRsThreads) void k_resample(rs_args A) {
 #pragma unroll
           for (unsigned q = 0; q < kPer; ++q) {
             const unsigned long long j = c * kPer + q;
-            if (j >= j0) rs_put(A, lds, j, (unsigned)(j - j0), cap.ifreq, te_unpack<K>(ws, q, sc, flip));
+            if (j >= j0) rs_put(A, lds, j, (unsigned)(j - j0), cap.ifreq, in_unpack<K>(ws, q, sc, flip));
           }
         } else {
           for (unsigned q = 0; q < kPer; ++q) {
             const unsigned long long j = c * kPer + q;
-            if (j >= j0 && j < jend) rs_put(A, lds, j, (unsigned)(j - j0), cap.ifreq, te_load<K>(cap.in, (size_t)j, sc, flip));
+            if (j >= j0 && j < jend) rs_put(A, lds, j, (unsigned)(j - j0), cap.ifreq, in_load<K>(cap.in, (size_t)j, sc, flip));
           }
         }
       }
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(kRsThreads) void k_resample(rs_args A) {
 #pragma unroll
       for (int k = 0; k < NB; ++k) {
         const unsigned t = tb + l + (unsigned)k * kRsThreads;
-        if (t < T) v[k] = te_load<K>(cap.in, (size_t)(j0 + t), sc, flip);
+        if (t < T) v[k] = in_load<K>(cap.in, (size_t)(j0 + t), sc, flip);
       }
 #pragma unroll
       for (int k = 0; k < NB; ++k) {
@@ -155,16 +154,6 @@ __global__ __launch_bounds__(kRsThreads) void k_resample(rs_args A) {
   }
 }
 
-int rs_kind(int in_format) {
-  switch (in_format) {
-    case LSDR_IN_CU8: return kTeU8;
-    case LSDR_IN_CS8: return kTeS8;
-    case LSDR_IN_CU16: case LSDR_IN_CS16: return kTe16;
-    case LSDR_IN_CF32: return kTeF32;
-  }
-  return -1;
-}
-
 // LDS row stride for a tile of M outputs: its N / D + 1 columns of halo behind M, made odd (consecutive rows land on different banks)
 unsigned rs_stride(unsigned M, unsigned N, unsigned D) { return (M + N / D + 1u) | 1u; }
 size_t rs_lds_bytes(unsigned M, unsigned N, unsigned D) { return (size_t)D * rs_stride(M, N, D) * sizeof(float2); }
@@ -192,18 +181,15 @@ void rs_launch(unsigned M, dim3 grid, size_t lds, hipStream_t s, const rs_args &
 struct lsdr_resample_batch {
   lsdr_ctx *ctx = nullptr;
   lsdr_resample_batch_cfg cfg{};
-  int kind = 0;
-  size_t item_bytes = 0;
+  lsdr_in_desc in{};
   unsigned M = 0;
   size_t lds = 0;
   rs_args A{};
-  rs_cap *h_caps = nullptr, *d_caps = nullptr;         // pinned / device
+  in_run<rs_cap> run;
   float2 *d_tab = nullptr;
   float *d_taps = nullptr;
   unsigned *d_offs = nullptr;
   std::vector<lsdr_resample_result> results;           // known at run_async: pure functions of the sizes
-  hipEvent_t ev_done = nullptr;
-  bool in_flight = false;
 };
 
 extern "C" {
@@ -242,12 +228,8 @@ int lsdr_resample_design(float omega, float rolloff, float rej, unsigned decim, 
 void lsdr_resample_batch_destroy(lsdr_resample_batch *b) {
   if (!b) return;
   (void)hipStreamSynchronize(b->ctx->stream);
-  if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-  if (b->d_caps) (void)hipFree(b->d_caps);
-  if (b->d_tab) (void)hipFree(b->d_tab);
-  if (b->d_taps) (void)hipFree(b->d_taps);
-  if (b->d_offs) (void)hipFree(b->d_offs);
-  if (b->h_caps) (void)hipHostFree(b->h_caps);
+  b->run.destroy();
+  lsdr_in_free({b->d_tab, b->d_taps, b->d_offs}, {});
   delete b;
 }
 
@@ -256,10 +238,7 @@ static int rs_build(lsdr_resample_batch *b) {
   const size_t B = (size_t)b->cfg.n_captures;
   const unsigned N = b->cfg.ncoeffs, D = b->cfg.decim;
   LSDR_HIP(hipSetDevice(c->device));
-  LSDR_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-  LSDR_HIP(hipHostMalloc((void **)&b->h_caps, B * sizeof(rs_cap), hipHostMallocDefault));
-  memset(b->h_caps, 0, B * sizeof(rs_cap));
-  LSDR_HIP(hipMalloc((void **)&b->d_caps, B * sizeof(rs_cap)));
+  LSDR_TRY(b->run.create(B));
   LSDR_HIP(hipMalloc((void **)&b->d_tab, 65536 * sizeof(float2)));
   LSDR_HIP(hipMalloc((void **)&b->d_taps, N * sizeof(float)));
   LSDR_HIP(hipMalloc((void **)&b->d_offs, N * sizeof(unsigned)));
@@ -276,20 +255,18 @@ static int rs_build(lsdr_resample_batch *b) {
   LSDR_HIP(hipMemcpy(b->d_offs, offs.data(), N * sizeof(unsigned), hipMemcpyHostToDevice));
   b->cfg.coeffs_host = nullptr;                              // (the caller's array is not kept)
   rs_args &A = b->A;
-  A.caps = b->d_caps; A.tab = b->d_tab; A.taps = b->d_taps; A.offs = b->d_offs;
+  A.caps = b->run.d_caps; A.tab = b->d_tab; A.taps = b->d_taps; A.offs = b->d_offs;
   A.N = N; A.D = D; A.M = b->M; A.S = S;
   A.magic = D > 1u ? (unsigned)((0x100000000ull + D - 1u) / D) : 0u;
-  A.in_scale = b->cfg.in_scale == 0.f ? 1.0f : b->cfg.in_scale;
-  A.in_flip = b->cfg.in_format == LSDR_IN_CU16 ? 0x80008000u : 0u;
+  A.in_scale = b->in.in_scale; A.in_flip = b->in.in_flip;
   return LSDR_OK;
 }
 
 int lsdr_resample_batch_create(lsdr_ctx *c, const lsdr_resample_batch_cfg *cfg, lsdr_resample_batch **out) {
   LSDR_ARG(c && cfg && out);
   if (cfg->n_captures < 1) { lsdr_set_error("resample_batch: n_captures must be at least 1 (got %d)", cfg->n_captures); return LSDR_E_ARG; }
-  const int kind = rs_kind(cfg->in_format);
-  if (kind < 0) { lsdr_set_error("resample_batch: in_format %d is none of LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32", cfg->in_format); return LSDR_E_ARG; }
-  if (!std::isfinite(cfg->in_scale) || cfg->in_scale < 0.f) { lsdr_set_error("resample_batch: in_scale must be finite and not negative"); return LSDR_E_ARG; }
+  lsdr_in_desc in;
+  LSDR_TRY(lsdr_in_describe("resample_batch", cfg->in_format, cfg->in_scale, &in));
   for (int i = 0; i < 6; ++i)
     if (cfg->reserved[i]) { lsdr_set_error("resample_batch: lsdr_resample_batch_cfg.reserved must be 0"); return LSDR_E_ARG; }
   if (!cfg->coeffs_host) { lsdr_set_error("resample_batch: coeffs_host is NULL"); return LSDR_E_ARG; }
@@ -299,9 +276,8 @@ int lsdr_resample_batch_create(lsdr_ctx *c, const lsdr_resample_batch_cfg *cfg, 
   const unsigned M = rs_tile(cfg->ncoeffs, cfg->decim);
   if (!M) { lsdr_set_error("resample_batch: no tile of ncoeffs %u, decim %u fits LDS", cfg->ncoeffs, cfg->decim); return LSDR_E_UNSUPPORTED; }
   lsdr_resample_batch *b = new lsdr_resample_batch();
-  b->ctx = c; b->cfg = *cfg; b->kind = kind; b->M = M;
+  b->ctx = c; b->cfg = *cfg; b->in = in; b->M = M;
   b->lds = rs_lds_bytes(M, cfg->ncoeffs, cfg->decim);
-  b->item_bytes = kind == kTeF32 ? 8 : (kind == kTe16 ? 4 : 2);
   b->results.assign((size_t)cfg->n_captures, lsdr_resample_result{});
   const int rc = rs_build(b);
   if (rc) { lsdr_resample_batch_destroy(b); return rc; }
@@ -315,27 +291,22 @@ int lsdr_resample_batch_run_async(lsdr_resample_batch *b, const void *const *iq_
                                   size_t cap_out) {
   LSDR_ARG(b && iq_dev && each && out_dev);
   const unsigned B = (unsigned)b->cfg.n_captures, N = b->cfg.ncoeffs, D = b->cfg.decim;
+  LSDR_TRY(lsdr_in_check_each("resample_batch", "tune", B, iq_dev, each, nullptr, nullptr, b->cfg.max_samples, b->in.item_bytes));
   for (unsigned i = 0; i < B; ++i) {
     const lsdr_capture_each &e = each[i];
-    if (e.n_samples > b->cfg.max_samples) { lsdr_set_error("resample_batch: capture %u: n_samples %zu exceeds max_samples %zu", i, e.n_samples, b->cfg.max_samples); return LSDR_E_ARG; }
-    if (!std::isfinite(e.tune) || !(fabsf(e.tune) < 0.5f)) { lsdr_set_error("resample_batch: capture %u: tune must be finite with |tune| < 0.5", i); return LSDR_E_ARG; }
-    for (int k = 0; k < 5; ++k)
-      if (e.reserved[k]) { lsdr_set_error("resample_batch: capture %u: lsdr_capture_each.reserved must be 0", i); return LSDR_E_ARG; }
-    if (!iq_dev[i] && e.n_samples) { lsdr_set_error("resample_batch: capture %u has samples and no pointer", i); return LSDR_E_ARG; }
-    if ((size_t)iq_dev[i] % b->item_bytes) { lsdr_set_error("resample_batch: capture %u: the input pointer is not aligned to the item size (%zu bytes)", i, b->item_bytes); return LSDR_E_ARG; }
     if ((size_t)out_dev[i] % 16u) { lsdr_set_error("resample_batch: capture %u: the output pointer is not aligned to 16 bytes", i); return LSDR_E_ARG; }
     const size_t want = e.n_samples >= N ? (e.n_samples - N) / D : 0;
     if (want > cap_out) { lsdr_set_error("resample_batch: capture %u: cap_out is %zu, the capture produces %zu items", i, cap_out, want); return LSDR_E_ARG; }
     if (want && !out_dev[i]) { lsdr_set_error("resample_batch: capture %u produces %zu items and has no output pointer", i, want); return LSDR_E_ARG; }
   }
-  if (b->in_flight) { lsdr_set_error("resample_batch: a run is in flight (lsdr_resample_batch_wait first)"); return LSDR_E_ARG; }
+  LSDR_TRY(b->run.idle("resample_batch", "lsdr_resample_batch_wait"));
   lsdr_ctx *c = b->ctx;
   LSDR_HIP(hipSetDevice(c->device));
   unsigned long long longest = 0;                            // the grid is sized for it; a shorter capture's workgroups leave at once
   for (unsigned i = 0; i < B; ++i) {
     const lsdr_capture_each &e = each[i];
     const unsigned long long produced = e.n_samples >= N ? (e.n_samples - N) / D : 0;
-    rs_cap &cap = b->h_caps[i];
+    rs_cap &cap = b->run.h_caps[i];
     cap.in = reinterpret_cast<const unsigned char *>(iq_dev[i]);
     cap.out = reinterpret_cast<float2 *>(out_dev[i]);
     cap.produced = produced;
@@ -349,27 +320,17 @@ int lsdr_resample_batch_run_async(lsdr_resample_batch *b, const void *const *iq_
   }
   const unsigned long long tiles = (longest + b->M - 1u) / b->M;
   if (tiles > 0x7fffffffull) { lsdr_set_error("resample_batch: %llu tiles exceed one launch", tiles); return LSDR_E_UNSUPPORTED; }
-  LSDR_HIP(hipMemcpyAsync(b->d_caps, b->h_caps, B * sizeof(rs_cap), hipMemcpyHostToDevice, c->stream));
+  LSDR_TRY(b->run.upload(c->stream));
   if (tiles) {
-    const dim3 grid((unsigned)tiles, B);
-    switch (b->kind) {
-      case kTeU8: rs_launch<kTeU8>(b->M, grid, b->lds, c->stream, b->A); break;
-      case kTeS8: rs_launch<kTeS8>(b->M, grid, b->lds, c->stream, b->A); break;
-      case kTe16: rs_launch<kTe16>(b->M, grid, b->lds, c->stream, b->A); break;
-      default: rs_launch<kTeF32>(b->M, grid, b->lds, c->stream, b->A); break;
-    }
+    in_dispatch(b->in.kind, [&](auto K) { rs_launch<K()>(b->M, dim3((unsigned)tiles, B), b->lds, c->stream, b->A); });
     LSDR_HIP(hipGetLastError());
   }
-  LSDR_HIP(hipEventRecord(b->ev_done, c->stream));
-  b->in_flight = true;
-  return LSDR_OK;
+  return b->run.mark(c->stream);
 }
 
 int lsdr_resample_batch_wait(lsdr_resample_batch *b, lsdr_resample_result *results) {
   LSDR_ARG(b);
-  if (!b->in_flight) { lsdr_set_error("resample_batch: no run in flight"); return LSDR_E_ARG; }
-  LSDR_HIP(hipEventSynchronize(b->ev_done));
-  b->in_flight = false;
+  LSDR_TRY(b->run.wait("resample_batch"));
   if (results) memcpy(results, b->results.data(), b->results.size() * sizeof(lsdr_resample_result));
   return LSDR_OK;
 }

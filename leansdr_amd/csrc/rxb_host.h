@@ -36,10 +36,7 @@ struct lsdr_rxb {
   size_t soft_cap;                 // soft symbols per capture in out_soft
   unsigned long long *d_counts;    // [n] contiguous: soft symbols of every capture after the launch
   hipEvent_t ev_pre, ev_tiles;      // hand-overs between the tile stream and the auxiliary stream (lsdr_rxb_launch with aux)
-  int in_format;                   // LSDR_IN_* of the captures' items (lsdr_capture_input_cfg)
-  int kind;                        // the kernels' kind (rxb_device.h: kRxbU8 …) and what goes with it
-  unsigned item_bytes, in_flip;
-  float in_scale;                  // 1: none
+  lsdr_in_desc in;                 // the captures' items (lsdr_capture_input_cfg): the kernels' kind (rxb_device.h: kRxbU8 …) and what goes with it
   // signal reports (lsdr_rxb_set_reports; off: rep_on false, nothing allocated, the kernels and launches of an object without them)
   bool rep_on;
   unsigned long long rep_period;   // as given
@@ -76,26 +73,27 @@ static rxb_geom rxb_geometry(const lsdr_rxb *b, size_t n_samples) {
   return g;
 }
 
+// rxb_device.h's kinds are capture_input.h's, so lsdr_in_desc::kind selects the kernels as it stands
+static_assert(kRxbU8 == kCapU8 && kRxbS8 == kCapS8 && kRxb16 == kCap16 && kRxbF32 == kCapF32, "one numbering of the kinds");
+
+// An object's in_format / in_scale (lsdr_capture_input_cfg) with the front end's own rule: cu8 without a scale has its own kernels, and
+// those have no scaler.
+int lsdr_rxb_describe_in(int in_format, float in_scale, lsdr_in_desc *out) {
+  LSDR_TRY(lsdr_in_describe("capture_batch", in_format, in_scale, out));
+  if (out->kind == kRxbU8 && out->in_scale != 1.0f) {
+    lsdr_set_error("capture_batch: cu8 captures take no in_scale (got %g): the cu8 kernels have no scaler", (double)in_scale); return LSDR_E_UNSUPPORTED;
+  }
+  return LSDR_OK;
+}
+
 // soft != 0: lsdr_softsymbol records out (rxb_device.h's soft tiles); pll_adjustment: cstln_receiver::pll_adjustment (sdr.h:777: divides
 // freq_beta only), 1 in leandvb's default graph, 6 behind viterbi_sync (leandvb.cc:498-501) — given here as the factor 1/6
 // in_format / in_scale: lsdr_capture_input_cfg (checked here).  cu8 without a scale has its own kernels.
 int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft, float pll_adjustment, int in_format, float in_scale, lsdr_rxb **out) {
   LSDR_ARG(c && cfg && out && cfg->n_captures >= 1 && cfg->n_captures <= 4096 && cfg->max_samples >= 4096);
   LSDR_ARG(cfg->anf == 0 || cfg->anf == 1);
-  int kind = kRxbU8; unsigned item_bytes = 2, in_flip = 0;
-  switch (in_format) {
-    case LSDR_IN_CU8: break;
-    case LSDR_IN_CS8: kind = kRxbS8; break;
-    case LSDR_IN_CU16: kind = kRxb16; item_bytes = 4; in_flip = 0x80008000u; break;
-    case LSDR_IN_CS16: kind = kRxb16; item_bytes = 4; break;
-    case LSDR_IN_CF32: kind = kRxbF32; item_bytes = 8; break;
-    default: lsdr_set_error("capture_batch: in_format %d is none of LSDR_IN_CU8 / CS8 / CU16 / CS16 / CF32", in_format); return LSDR_E_ARG;
-  }
-  if (!(in_scale >= 0.f) || std::isinf(in_scale)) { lsdr_set_error("capture_batch: in_scale must be finite and not negative"); return LSDR_E_ARG; }
-  if (in_scale == 0.f) in_scale = 1.0f;
-  if (kind == kRxbU8 && in_scale != 1.0f) {
-    lsdr_set_error("capture_batch: cu8 captures take no in_scale (got %g): the cu8 kernels have no scaler", (double)in_scale); return LSDR_E_UNSUPPORTED;
-  }
+  lsdr_in_desc in;
+  LSDR_TRY(lsdr_rxb_describe_in(in_format, in_scale, &in));
   lsdr_rx_cfg rc;
   memset(&rc, 0, sizeof(rc));
   rc.sampler = LSDR_SAMP_LINEAR; rc.cstln = LSDR_QPSK; rc.fec = cfg->fec; rc.omega = cfg->omega; rc.freq = 0.f;
@@ -108,10 +106,10 @@ int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft,
     return LSDR_E_ARG;
   }
   rc.tile_len = L; rc.tile_warmup = W;
-  if (kind != kRxbU8) {
+  if (in.kind != kRxbU8) {
     // the tiles address a capture with 32-bit byte offsets (rxb_tile: src_off below 0xfff00000, plus the offset inside the tile)
-    if ((unsigned long long)cfg->max_samples * item_bytes >= 0xfff00000ull || ((unsigned long long)L + W) * item_bytes >= 0x100000ull) {
-      lsdr_set_error("capture_batch: %zu samples of %u bytes (tile_len %u) are beyond the tiles' 32-bit buffer offsets", cfg->max_samples, item_bytes, L);
+    if ((unsigned long long)cfg->max_samples * in.item_bytes >= 0xfff00000ull || ((unsigned long long)L + W) * in.item_bytes >= 0x100000ull) {
+      lsdr_set_error("capture_batch: %zu samples of %u bytes (tile_len %u) are beyond the tiles' 32-bit buffer offsets", cfg->max_samples, in.item_bytes, L);
       return LSDR_E_UNSUPPORTED;
     }
   }
@@ -121,7 +119,7 @@ int lsdr_rxb_create_in(lsdr_ctx *c, const lsdr_capture_batch_cfg *cfg, int soft,
   b->ctx = c; b->proto = proto; b->n = (unsigned)cfg->n_captures; b->max_samples = cfg->max_samples; b->anf = cfg->anf;
   b->Lc = L / kChunk; b->Wc = W / kChunk;
   b->soft = soft != 0;
-  b->in_format = in_format; b->kind = kind; b->item_bytes = item_bytes; b->in_flip = in_flip; b->in_scale = in_scale;
+  b->in = in;
   b->pre_block = (L % 4096u) ? 2048u : 4096u;
   b->nk = cfg->notch_k > 0.f ? cfg->notch_k : 0.002f;                          // sdr.h:56
   b->notch_decimation = cfg->notch_decimation > 0 ? cfg->notch_decimation : 1024 * kDetN;
@@ -283,7 +281,7 @@ static void rxb_fill_args(const lsdr_rxb *b, rxb_args &A) {
   A.tile_chunks = b->Lc; A.warm_chunks = b->Wc; A.pre_block = b->pre_block; A.pre_look = b->pre_look;
   A.nk = b->nk; A.l2omk = (float)log2((double)(1.0f - b->nk));
   rx_fill_consts(b->proto, A.C, A.T);
-  A.in_scale = b->in_scale; A.in_flip = b->in_flip;
+  A.in_scale = b->in.in_scale; A.in_flip = b->in.in_flip;
   A.rep = b->d_rep; A.rep_period = b->rep_period_k;
 }
 
@@ -303,31 +301,18 @@ template <int K> static rxb_kernel_t rxb_tiles_rep_of(bool notch, bool soft) {
   return notch ? k_rxb_tiles_rep<true, false, K> : k_rxb_tiles_rep<false, false, K>;
 }
 static rxb_kernel_t rxb_kernel_tiles_rep(int kind, bool notch, bool soft) {
-  switch (kind) {
-    case kRxbS8: return rxb_tiles_rep_of<kRxbS8>(notch, soft);
-    case kRxb16: return rxb_tiles_rep_of<kRxb16>(notch, soft);
-    case kRxbF32: return rxb_tiles_rep_of<kRxbF32>(notch, soft);
-  }
-  return rxb_tiles_rep_of<kRxbU8>(notch, soft);
+  return in_dispatch(kind, [&](auto K) { return rxb_tiles_rep_of<K()>(notch, soft); });
 }
 static rxb_kernel_t rxb_kernel_tiles(int kind, bool notch, bool soft) {
-  switch (kind) {
-    case kRxbS8: return rxb_tiles_of<kRxbS8>(notch, soft);
-    case kRxb16: return rxb_tiles_of<kRxb16>(notch, soft);
-    case kRxbF32: return rxb_tiles_of<kRxbF32>(notch, soft);
-  }
-  if (soft) return notch ? k_rxb_tiles_soft<true> : k_rxb_tiles_soft<false>;
-  return notch ? k_rxb_tiles<true> : k_rxb_tiles<false>;
+  return in_dispatch(kind, [&](auto K) -> rxb_kernel_t {
+    if constexpr (K() != kRxbU8) return rxb_tiles_of<K()>(notch, soft);
+    else if (soft) return notch ? k_rxb_tiles_soft<true> : k_rxb_tiles_soft<false>;
+    else return notch ? k_rxb_tiles<true> : k_rxb_tiles<false>;
+  });
 }
-static rxb_kernel_t rxb_kernel_detect(int kind) {
-  return kind == kRxbS8 ? k_rxb_detect_fft<kRxbS8> : kind == kRxb16 ? k_rxb_detect_fft<kRxb16> : kind == kRxbF32 ? k_rxb_detect_fft<kRxbF32> : k_rxb_detect_fft<kRxbU8>;
-}
-static rxb_kernel_t rxb_kernel_pre(int kind) {
-  return kind == kRxbS8 ? k_rxb_notch_pre<kRxbS8> : kind == kRxb16 ? k_rxb_notch_pre<kRxb16> : kind == kRxbF32 ? k_rxb_notch_pre<kRxbF32> : k_rxb_notch_pre<kRxbU8>;
-}
-static rxb_dump_kernel_t rxb_kernel_dump(int kind) {
-  return kind == kRxbS8 ? k_rxb_notch_dump<kRxbS8> : kind == kRxb16 ? k_rxb_notch_dump<kRxb16> : kind == kRxbF32 ? k_rxb_notch_dump<kRxbF32> : k_rxb_notch_dump<kRxbU8>;
-}
+static rxb_kernel_t rxb_kernel_detect(int kind) { return in_dispatch(kind, [](auto K) -> rxb_kernel_t { return k_rxb_detect_fft<K()>; }); }
+static rxb_kernel_t rxb_kernel_pre(int kind) { return in_dispatch(kind, [](auto K) -> rxb_kernel_t { return k_rxb_notch_pre<K()>; }); }
+static rxb_dump_kernel_t rxb_kernel_dump(int kind) { return in_dispatch(kind, [](auto K) -> rxb_dump_kernel_t { return k_rxb_notch_dump<K()>; }); }
 
 // capture i's constructed loop state under set_freq(tune): what lsdr_rx_create leaves for cfg.freq = tune (sdr.h:745-770; leandvb calls
 // set_freq only for a nonzero --tune, leandvb.cc:483-487)
@@ -355,11 +340,8 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, const size_t *n_samples,
   size_t longest = 0;
   rxb_geom gmax; memset(&gmax, 0, sizeof(gmax));
   std::vector<rxb_geom> geo(b->n);
+  LSDR_TRY(lsdr_in_check_each("capture_batch", "tune", b->n, iq, nullptr, n_samples, tune, b->max_samples, b->in.item_bytes));
   for (unsigned i = 0; i < b->n; ++i) {
-    if (n_samples[i] > b->max_samples) { lsdr_set_error("capture_batch: capture %u has %zu samples, created for %zu", i, n_samples[i], b->max_samples); return LSDR_E_ARG; }
-    if (!std::isfinite(tune[i]) || !(fabsf(tune[i]) < 0.5f)) { lsdr_set_error("capture_batch: capture %u: tune must be finite and inside (-0.5, 0.5) cycles per sample", i); return LSDR_E_ARG; }
-    if (!iq[i] && n_samples[i]) { lsdr_set_error("capture_batch: capture %u has no samples pointer", i); return LSDR_E_ARG; }
-    if (((unsigned long long)iq[i] & (unsigned long long)(b->item_bytes - 1)) != 0) { lsdr_set_error("capture_batch: capture %u is not aligned to its items", i); return LSDR_E_ARG; }
     const rxb_geom g = rxb_geometry(b, n_samples[i]);
     geo[i] = g;
     if (n_samples[i] > longest) longest = n_samples[i];
@@ -420,16 +402,16 @@ int lsdr_rxb_launch(lsdr_rxb *b, const void *const *iq, const size_t *n_samples,
   rxb_args A;
   rxb_fill_args(b, A);
   if (notch) {
-    hipLaunchKernelGGL(rxb_kernel_detect(b->kind), dim3(2 * gmax.n_det, b->n), dim3(256), 0, sa, A);
+    hipLaunchKernelGGL(rxb_kernel_detect(b->in.kind), dim3(2 * gmax.n_det, b->n), dim3(256), 0, sa, A);
     hipLaunchKernelGGL(k_rxb_detect_peaks, dim3(gmax.n_det, b->n), dim3(256), 0, sa, A);
     hipLaunchKernelGGL(k_rxb_iv, dim3((b->n + 63) / 64), dim3(64), 0, sa, A, b->n);
-    hipLaunchKernelGGL(rxb_kernel_pre(b->kind), dim3(gmax.n_pre, b->n), dim3(256), 0, sa, A);
+    hipLaunchKernelGGL(rxb_kernel_pre(b->in.kind), dim3(gmax.n_pre, b->n), dim3(256), 0, sa, A);
     LSDR_HIP(hipGetLastError());
   }
   const unsigned blocks = 1 + (gmax.n_tiles - 1 + 63) / 64;
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_pre, sa)); LSDR_HIP(hipStreamWaitEvent(st, b->ev_pre, 0)); }
   if (b->timing) { LSDR_HIP(hipEventRecord(b->tev0, st)); }
-  hipLaunchKernelGGL(b->rep_on ? rxb_kernel_tiles_rep(b->kind, notch, b->soft) : rxb_kernel_tiles(b->kind, notch, b->soft), dim3(blocks, b->n), dim3(64), 0, st, A);
+  hipLaunchKernelGGL(b->rep_on ? rxb_kernel_tiles_rep(b->in.kind, notch, b->soft) : rxb_kernel_tiles(b->in.kind, notch, b->soft), dim3(blocks, b->n), dim3(64), 0, st, A);
   if (b->timing) { LSDR_HIP(hipEventRecord(b->tev1, st)); b->tev_pending = true; }
   if (aux) { LSDR_HIP(hipEventRecord(b->ev_tiles, st)); LSDR_HIP(hipStreamWaitEvent(sa, b->ev_tiles, 0)); }
   const int R = r->tabs.nrotations;
@@ -492,7 +474,7 @@ int lsdr_rxb_notched(lsdr_rxb *b, unsigned i, lsdr_cf32 *out_dev, size_t n) {
   // (a run without a detect point launched no detect chain: the pass-through interval 0 is written here)
   if (!b->any_det) hipLaunchKernelGGL(k_rxb_iv, dim3((b->n + 63) / 64), dim3(64), 0, b->ctx->stream, A, b->n);
   const unsigned segs = (unsigned)((n + b->pre_block - 1) / b->pre_block);
-  hipLaunchKernelGGL(rxb_kernel_dump(b->kind), dim3((segs + 63) / 64), dim3(64), 0, b->ctx->stream, A, i, (unsigned long long)n, reinterpret_cast<float2 *>(out_dev));
+  hipLaunchKernelGGL(rxb_kernel_dump(b->in.kind), dim3((segs + 63) / 64), dim3(64), 0, b->ctx->stream, A, i, (unsigned long long)n, reinterpret_cast<float2 *>(out_dev));
   LSDR_HIP(hipGetLastError());
   LSDR_HIP(hipStreamSynchronize(b->ctx->stream));
   return LSDR_OK;

@@ -17,8 +17,7 @@
 // depend on the sample's index alone — the same bits alone, in any batch, with any slab_rows and any number of stages per pass.
 // Every kernel leaves by the capture's own row count: nothing behind a capture's last fetched block is read.
 #include <cmath>
-#include "lsdr_internal.h"
-#include "tune_est_device.h"
+#include "capture_input.h"
 #include "spectrum_batch_device.h"
 
 namespace {
@@ -51,9 +50,8 @@ __global__ __launch_bounds__(kSbThreads) void k_sb_power(sb_args A) {
   if (valid > per) valid = per;
   extern __shared__ __attribute__((aligned(16))) char sb_smem[];
   float2 *d = reinterpret_cast<float2 *>(sb_smem), *w = d + kSbDataLds;
-  constexpr unsigned kB = te_item<K>::kBytes, kPer = 16u / kB;
+  constexpr unsigned kB = in_item<K>::kBytes, kPer = 16u / kB;
   const unsigned t = threadIdx.x;
-  const float sc = A.in_scale; const unsigned flip = A.in_flip;
   const bool vec = ((size_t)cap.in & 15u) == 0;              // (a block is a multiple of 16 bytes: the capture's own alignment decides)
   for (unsigned c = t; c < kSbPoints / kPer; c += kSbThreads) {
     const unsigned idx = c * kPer, u = idx >> logn, within = idx & (nfft - 1u);
@@ -65,15 +63,7 @@ __global__ __launch_bounds__(kSbThreads) void k_sb_power(sb_args A) {
     const unsigned long long blk = sb_block_of_row((unsigned long long)A.slab_base + local0 + u + 1ull, logn, A.decimation);
     const unsigned char *src = cap.in + ((size_t)blk << logn) * kB;
     float2 z[kPer];
-    if (vec) {
-      const uint4 v4 = *reinterpret_cast<const uint4 *>(src + (size_t)within * kB);
-      const unsigned ws[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (unsigned q = 0; q < kPer; ++q) z[q] = te_unpack<K>(ws, q, sc, flip);
-    } else {
-#pragma unroll
-      for (unsigned q = 0; q < kPer; ++q) z[q] = te_load<K>(src, within + q, sc, flip);
-    }
+    in_piece<K>(src, within, vec, A.in_scale, A.in_flip, z);
 #pragma unroll
     for (unsigned q = 0; q < kPer; ++q)                      // the bit-reversal permutation (dsp.h:84-92): position P holds in[brev(P)]
       d[sb_dp((u << logn) | (__brev(within + q) >> (32u - logn)))] = z[q];
@@ -143,34 +133,22 @@ __global__ __launch_bounds__(64) void k_sb_bands(sb_args A) {
   A.sums[((size_t)blockIdx.y * A.max_rows + A.slab_base + r) * 3u + band] = sb_band_sum(row, i0, i1, 1u << A.logn);
 }
 
-int sb_kind(int in_format) {
-  switch (in_format) {
-    case LSDR_IN_CU8: return kTeU8;
-    case LSDR_IN_CS8: return kTeS8;
-    case LSDR_IN_CU16: case LSDR_IN_CS16: return kTe16;
-    case LSDR_IN_CF32: return kTeF32;
-  }
-  return -1;
-}
-
 }  // namespace
 
 struct lsdr_spectrum_batch {
   lsdr_ctx *ctx = nullptr;
   lsdr_spectrum_batch_cfg cfg{};
-  int kind = 0;
-  size_t item_bytes = 0;
+  lsdr_in_desc in{};
   unsigned logn = 0;
   size_t max_rows = 0, rows_alloc = 0;            // rows_alloc: max_rows, at least 1 (the strides of rows / sums)
   float kavg = 0.f;
   sb_args A{};
-  sb_cap *h_caps = nullptr, *d_caps = nullptr;    // pinned / device
+  in_run<sb_cap> run;
   lsdr_spectrum_result *h_res = nullptr;          // pinned
   float *h_sums = nullptr, *d_sums = nullptr;     // pinned / device
   float2 *d_om = nullptr;
   float *d_scratch = nullptr, *d_avg = nullptr, *d_rows = nullptr;
-  hipEvent_t ev_done = nullptr;
-  bool in_flight = false, have = false;           // have: a finished run's results are there for the accessors
+  bool have = false;                              // a finished run's results are there for the accessors
 };
 
 extern "C" {
@@ -178,12 +156,8 @@ extern "C" {
 void lsdr_spectrum_batch_destroy(lsdr_spectrum_batch *b) {
   if (!b) return;
   (void)hipStreamSynchronize(b->ctx->stream);
-  if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-  (void)hipFree(b->d_caps); (void)hipFree(b->d_sums); (void)hipFree(b->d_om);
-  (void)hipFree(b->d_scratch); (void)hipFree(b->d_avg); (void)hipFree(b->d_rows);
-  if (b->h_caps) (void)hipHostFree(b->h_caps);
-  if (b->h_res) (void)hipHostFree(b->h_res);
-  if (b->h_sums) (void)hipHostFree(b->h_sums);
+  b->run.destroy();
+  lsdr_in_free({b->d_sums, b->d_om, b->d_scratch, b->d_avg, b->d_rows}, {b->h_res, b->h_sums});
   delete b;
 }
 
@@ -191,12 +165,9 @@ static int sb_build(lsdr_spectrum_batch *b) {
   lsdr_ctx *c = b->ctx;
   const size_t B = (size_t)b->cfg.n_captures, nfft = (size_t)b->cfg.nfft;
   LSDR_HIP(hipSetDevice(c->device));
-  LSDR_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-  LSDR_HIP(hipHostMalloc((void **)&b->h_caps, B * sizeof(sb_cap), hipHostMallocDefault));
+  LSDR_TRY(b->run.create(B));
   LSDR_HIP(hipHostMalloc((void **)&b->h_res, B * sizeof(lsdr_spectrum_result), hipHostMallocDefault));
-  memset(b->h_caps, 0, B * sizeof(sb_cap));
   memset(b->h_res, 0, B * sizeof(lsdr_spectrum_result));
-  LSDR_HIP(hipMalloc((void **)&b->d_caps, B * sizeof(sb_cap)));
   LSDR_HIP(hipMalloc((void **)&b->d_om, nfft * sizeof(float2)));
   LSDR_HIP(hipMalloc((void **)&b->d_scratch, B * b->cfg.slab_rows * nfft * sizeof(float)));
   LSDR_HIP(hipMalloc((void **)&b->d_avg, B * nfft * sizeof(float)));
@@ -209,22 +180,20 @@ static int sb_build(lsdr_spectrum_batch *b) {
   notch_detect_twiddles((int)nfft, true, om);
   LSDR_HIP(hipMemcpy(b->d_om, om.data(), nfft * sizeof(float2), hipMemcpyHostToDevice));
   sb_args &A = b->A;
-  A.caps = b->d_caps; A.om = b->d_om; A.scratch = b->d_scratch; A.avg = b->d_avg; A.rows = b->d_rows; A.sums = b->d_sums;
+  A.caps = b->run.d_caps; A.om = b->d_om; A.scratch = b->d_scratch; A.avg = b->d_avg; A.rows = b->d_rows; A.sums = b->d_sums;
   A.max_rows = b->rows_alloc; A.slab_rows = b->cfg.slab_rows; A.slab_base = 0;
   A.logn = b->logn; A.decimation = b->cfg.decimation; A.stages = b->cfg.stages_per_pass;
   A.bwslots = (int)((b->cfg.bandwidth / 4) * b->cfg.nfft);
-  A.in_scale = b->cfg.in_scale == 0.f ? 1.0f : b->cfg.in_scale;
+  A.in_scale = b->in.in_scale; A.in_flip = b->in.in_flip;
   A.kavg = b->kavg; A.invn = (float)(1.0 / (double)nfft);
-  A.in_flip = b->cfg.in_format == LSDR_IN_CU16 ? 0x80008000u : 0u;
   return LSDR_OK;
 }
 
 int lsdr_spectrum_batch_create(lsdr_ctx *c, const lsdr_spectrum_batch_cfg *cfg, lsdr_spectrum_batch **out) {
   LSDR_ARG(c && cfg && out);
   if (cfg->n_captures < 1 || cfg->n_captures > 65535) { lsdr_set_error("spectrum_batch: n_captures must be 1 … 65535 (got %d)", cfg->n_captures); return LSDR_E_ARG; }
-  const int kind = sb_kind(cfg->in_format);
-  if (kind < 0) { lsdr_set_error("spectrum_batch: in_format %d is none of LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32", cfg->in_format); return LSDR_E_ARG; }
-  if (!std::isfinite(cfg->in_scale) || cfg->in_scale < 0.f) { lsdr_set_error("spectrum_batch: in_scale must be finite and not negative"); return LSDR_E_ARG; }
+  lsdr_in_desc in;
+  LSDR_TRY(lsdr_in_describe("spectrum_batch", cfg->in_format, cfg->in_scale, &in));
   if (cfg->nfft < 64 || cfg->nfft > 4096 || (cfg->nfft & (cfg->nfft - 1))) {
     lsdr_set_error("spectrum_batch: nfft must be a power of two, 64 … 4096 (got %d)", cfg->nfft); return LSDR_E_ARG;
   }
@@ -243,8 +212,7 @@ int lsdr_spectrum_batch_create(lsdr_ctx *c, const lsdr_spectrum_batch_cfg *cfg, 
   for (int i = 0; i < 5; ++i)
     if (cfg->reserved[i]) { lsdr_set_error("spectrum_batch: lsdr_spectrum_batch_cfg.reserved must be 0"); return LSDR_E_ARG; }
   lsdr_spectrum_batch *b = new lsdr_spectrum_batch();
-  b->ctx = c; b->cfg = *cfg; b->kind = kind;
-  b->item_bytes = kind == kTeF32 ? 8 : (kind == kTe16 ? 4 : 2);
+  b->ctx = c; b->cfg = *cfg; b->in = in;
   for (int t = cfg->nfft; t > 1; t >>= 1) ++b->logn;
   b->kavg = cfg->kavg == 0.f ? (float)0.1 : cfg->kavg;
   if (!b->cfg.stages_per_pass) b->cfg.stages_per_pass = kSbMaxStages;
@@ -273,21 +241,8 @@ unsigned lsdr_spectrum_batch_slab_rows(const lsdr_spectrum_batch *b) { return b 
 int lsdr_spectrum_batch_run_async(lsdr_spectrum_batch *b, const void *const *iq_dev, const lsdr_capture_each *each) {
   LSDR_ARG(b && iq_dev && each);
   const unsigned B = (unsigned)b->cfg.n_captures;
-  for (unsigned i = 0; i < B; ++i) {
-    if (each[i].n_samples > b->cfg.max_samples) {
-      lsdr_set_error("spectrum_batch: capture %u has %zu samples, max_samples is %zu", i, each[i].n_samples, b->cfg.max_samples); return LSDR_E_ARG;
-    }
-    if (!std::isfinite(each[i].tune) || std::fabs(each[i].tune) >= 0.5f) {
-      lsdr_set_error("spectrum_batch: capture %u: the centre must be finite and below 0.5 cycles per sample in magnitude", i); return LSDR_E_ARG;
-    }
-    for (int k = 0; k < 5; ++k)
-      if (each[i].reserved[k]) { lsdr_set_error("spectrum_batch: lsdr_capture_each.reserved must be 0 (capture %u)", i); return LSDR_E_ARG; }
-    if (!iq_dev[i] && each[i].n_samples) { lsdr_set_error("spectrum_batch: capture %u has samples and no pointer", i); return LSDR_E_ARG; }
-    if ((size_t)iq_dev[i] % b->item_bytes) {
-      lsdr_set_error("spectrum_batch: capture %u: the pointer is not aligned to the item size (%zu bytes)", i, b->item_bytes); return LSDR_E_ARG;
-    }
-  }
-  if (b->in_flight) { lsdr_set_error("spectrum_batch: a run is in flight (lsdr_spectrum_batch_wait first)"); return LSDR_E_ARG; }
+  LSDR_TRY(lsdr_in_check_each("spectrum_batch", "the centre", B, iq_dev, each, nullptr, nullptr, b->cfg.max_samples, b->in.item_bytes));
+  LSDR_TRY(b->run.idle("spectrum_batch", "lsdr_spectrum_batch_wait"));
   lsdr_ctx *c = b->ctx;
   LSDR_HIP(hipSetDevice(c->device));
   b->have = false;
@@ -298,7 +253,7 @@ int lsdr_spectrum_batch_run_async(lsdr_spectrum_batch *b, const void *const *iq_
     const size_t rows = (size_t)sb_rows(blocks, b->logn, b->cfg.decimation);
     const float center_freq = each[i].tune * 1.0f;           // *freq_tap * tap_multiplier
     const int icf = (int)floor((double)(center_freq * N) + 0.5);
-    sb_cap &cap = b->h_caps[i];
+    sb_cap &cap = b->run.h_caps[i];
     cap.in = reinterpret_cast<const unsigned char *>(iq_dev[i]);
     cap.rows = (unsigned)rows; cap.icf = icf;
     lsdr_spectrum_result &r = b->h_res[i];
@@ -306,7 +261,7 @@ int lsdr_spectrum_batch_run_async(lsdr_spectrum_batch *b, const void *const *iq_
     r.consumed = (uint64_t)blocks << b->logn; r.rows = rows; r.icf = b->cfg.bandwidth > 0 ? icf : 0;
     if (rows > longest) longest = rows;
   }
-  LSDR_HIP(hipMemcpyAsync(b->d_caps, b->h_caps, B * sizeof(sb_cap), hipMemcpyHostToDevice, c->stream));
+  LSDR_TRY(b->run.upload(c->stream));
   const unsigned slab = b->cfg.slab_rows, per = kSbPoints >> b->logn;
   const size_t lds = ((size_t)kSbDataLds + sb_tw_lds((unsigned)N)) * sizeof(float2);
   for (size_t base = 0; base < longest; base += slab) {      // (over slabs, never over rows)
@@ -314,31 +269,22 @@ int lsdr_spectrum_batch_run_async(lsdr_spectrum_batch *b, const void *const *iq_
     A.slab_base = (unsigned)base;
     const unsigned here = longest - base < slab ? (unsigned)(longest - base) : slab;    // the longest capture's rows in this slab
     const dim3 grid((here + per - 1u) / per, B), wg(kSbThreads);
-    switch (b->kind) {
-      case kTeU8: hipLaunchKernelGGL(k_sb_power<kTeU8>, grid, wg, lds, c->stream, A); break;
-      case kTeS8: hipLaunchKernelGGL(k_sb_power<kTeS8>, grid, wg, lds, c->stream, A); break;
-      case kTe16: hipLaunchKernelGGL(k_sb_power<kTe16>, grid, wg, lds, c->stream, A); break;
-      default: hipLaunchKernelGGL(k_sb_power<kTeF32>, grid, wg, lds, c->stream, A); break;
-    }
+    in_dispatch(b->in.kind, [&](auto K) { hipLaunchKernelGGL(k_sb_power<K()>, grid, wg, lds, c->stream, A); });
     hipLaunchKernelGGL(k_sb_average, dim3(((unsigned)N + 255u) / 256u, B), dim3(256), 0, c->stream, A);
     if (b->d_sums) hipLaunchKernelGGL(k_sb_bands, dim3((here * 3u + 63u) / 64u, B), dim3(64), 0, c->stream, A);
   }
   LSDR_HIP(hipGetLastError());
   if (b->d_sums)
     for (unsigned i = 0; i < B; ++i)
-      if (b->h_caps[i].rows)
+      if (b->run.h_caps[i].rows)
         LSDR_HIP(hipMemcpyAsync(b->h_sums + (size_t)i * b->rows_alloc * 3, b->d_sums + (size_t)i * b->rows_alloc * 3,
-                                (size_t)b->h_caps[i].rows * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  LSDR_HIP(hipEventRecord(b->ev_done, c->stream));
-  b->in_flight = true;
-  return LSDR_OK;
+                                (size_t)b->run.h_caps[i].rows * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  return b->run.mark(c->stream);
 }
 
 int lsdr_spectrum_batch_wait(lsdr_spectrum_batch *b, lsdr_spectrum_result *results) {
   LSDR_ARG(b);
-  if (!b->in_flight) { lsdr_set_error("spectrum_batch: no run in flight"); return LSDR_E_ARG; }
-  LSDR_HIP(hipEventSynchronize(b->ev_done));
-  b->in_flight = false;
+  LSDR_TRY(b->run.wait("spectrum_batch"));
   b->have = true;
   if (results) memcpy(results, b->h_res, (size_t)b->cfg.n_captures * sizeof(lsdr_spectrum_result));
   return LSDR_OK;
@@ -347,7 +293,7 @@ int lsdr_spectrum_batch_wait(lsdr_spectrum_batch *b, lsdr_spectrum_result *resul
 static int sb_accessor(const lsdr_spectrum_batch *b, int i) {
   LSDR_ARG(b);
   if (i < 0 || i >= b->cfg.n_captures) { lsdr_set_error("spectrum_batch: capture %d of %d", i, b->cfg.n_captures); return LSDR_E_ARG; }
-  if (b->in_flight || !b->have) { lsdr_set_error("spectrum_batch: no finished run (lsdr_spectrum_batch_wait first)"); return LSDR_E_ARG; }
+  if (b->run.in_flight || !b->have) { lsdr_set_error("spectrum_batch: no finished run (lsdr_spectrum_batch_wait first)"); return LSDR_E_ARG; }
   return LSDR_OK;
 }
 

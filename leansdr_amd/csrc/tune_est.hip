@@ -18,7 +18,7 @@
 // of its converted samples — the same bits alone, in any batch, in any place of it, and for every format that converts to the same floats.
 // Both kernels leave by the capture's own block count: nothing is read behind block M − 1 of a capture, and nothing at all of one with M = 0.
 #include <cmath>
-#include "lsdr_internal.h"
+#include "capture_input.h"
 #include "tune_est_device.h"
 
 namespace {
@@ -50,21 +50,23 @@ __global__ __launch_bounds__(256) void k_te_block(te_args A) {
   if (blockIdx.x >= cap.blocks) return;
   __shared__ float2 x[kTeN];
   __shared__ float red[4];
-  constexpr unsigned kB = te_item<K>::kBytes, kPer = 16u / kB;
+  constexpr unsigned kB = in_item<K>::kBytes, kPer = 16u / kB;
   const unsigned t = threadIdx.x;
   const unsigned char *src = cap.in + (size_t)blockIdx.x * kTeN * kB;
-  const float sc = A.in_scale; const unsigned flip = A.in_flip;
-  if (((size_t)src & 15u) == 0) {                            // (a block is a multiple of 16 bytes: the capture's own alignment decides)
+  // One 16-byte piece per thread and pass.  The alignment is decided once, in front of the loop, and the loop stays rolled: the registers
+  // of this kernel are the FFT's, and a workgroup's loads overlap with the FFTs of the others on its CU.
+  auto stage = [&](auto wide) {
+#pragma unroll 1
     for (unsigned l = 0; l < kTeN / (256u * kPer); ++l) {
       const unsigned s0 = (l * 256u + t) * kPer;
-      const uint4 w = *reinterpret_cast<const uint4 *>(src + (size_t)s0 * kB);
-      const unsigned ws[4] = {w.x, w.y, w.z, w.w};
+      float2 z[kPer];
+      in_piece<K>(src, s0, wide(), A.in_scale, A.in_flip, z);
 #pragma unroll
-      for (unsigned q = 0; q < kPer; ++q) x[s0 + q] = te_unpack<K>(ws, q, sc, flip);
+      for (unsigned q = 0; q < kPer; ++q) x[s0 + q] = z[q];
     }
-  } else {
-    for (unsigned l = 0; l < kTeN / 256u; ++l) x[l * 256u + t] = te_load<K>(src, l * 256u + t, sc, flip);
-  }
+  };
+  if (((size_t)src & 15u) == 0) stage(std::true_type());     // (a block is a multiple of 16 bytes: the capture's own alignment decides)
+  else stage(std::false_type());
   __syncthreads();
   float p = 0.f;
   for (unsigned i = 0; i < kTeN / 256u; ++i) { const float2 z = x[t + 256u * i]; p += z.x * z.x + z.y * z.y; }
@@ -120,31 +122,18 @@ __global__ __launch_bounds__(256) void k_te_peak(te_args A) {
   }
 }
 
-int te_kind(int in_format) {
-  switch (in_format) {
-    case LSDR_IN_CU8: return kTeU8;
-    case LSDR_IN_CS8: return kTeS8;
-    case LSDR_IN_CU16: case LSDR_IN_CS16: return kTe16;
-    case LSDR_IN_CF32: return kTeF32;
-  }
-  return -1;
-}
-
 }  // namespace
 
 struct lsdr_tune_est {
   lsdr_ctx *ctx = nullptr;
   lsdr_tune_est_cfg cfg{};
   unsigned blocks = 0;                 // cfg.blocks with the default filled in
-  int kind = 0;
-  size_t item_bytes = 0;
+  lsdr_in_desc in{};
   te_args A{};
-  te_cap *h_caps = nullptr, *d_caps = nullptr;        // pinned / device
+  in_run<te_cap> run;
   te_record *h_rec = nullptr, *d_rec = nullptr;       // pinned / device
   float2 *d_tw = nullptr;
   float *d_rows = nullptr;
-  hipEvent_t ev_done = nullptr;
-  bool in_flight = false;
 };
 
 extern "C" {
@@ -152,13 +141,8 @@ extern "C" {
 void lsdr_tune_est_destroy(lsdr_tune_est *e) {
   if (!e) return;
   (void)hipStreamSynchronize(e->ctx->stream);
-  if (e->ev_done) (void)hipEventDestroy(e->ev_done);
-  if (e->d_caps) (void)hipFree(e->d_caps);
-  if (e->d_rec) (void)hipFree(e->d_rec);
-  if (e->d_tw) (void)hipFree(e->d_tw);
-  if (e->d_rows) (void)hipFree(e->d_rows);
-  if (e->h_caps) (void)hipHostFree(e->h_caps);
-  if (e->h_rec) (void)hipHostFree(e->h_rec);
+  e->run.destroy();
+  lsdr_in_free({e->d_rec, e->d_tw, e->d_rows}, {e->h_rec});
   delete e;
 }
 
@@ -166,12 +150,9 @@ static int te_build(lsdr_tune_est *e) {
   lsdr_ctx *c = e->ctx;
   const size_t B = (size_t)e->cfg.n_captures;
   LSDR_HIP(hipSetDevice(c->device));
-  LSDR_HIP(hipEventCreateWithFlags(&e->ev_done, hipEventDisableTiming));
-  LSDR_HIP(hipHostMalloc((void **)&e->h_caps, B * sizeof(te_cap), hipHostMallocDefault));
+  LSDR_TRY(e->run.create(B));
   LSDR_HIP(hipHostMalloc((void **)&e->h_rec, B * sizeof(te_record), hipHostMallocDefault));
-  memset(e->h_caps, 0, B * sizeof(te_cap));
   memset(e->h_rec, 0, B * sizeof(te_record));
-  LSDR_HIP(hipMalloc((void **)&e->d_caps, B * sizeof(te_cap)));
   LSDR_HIP(hipMalloc((void **)&e->d_rec, B * sizeof(te_record)));
   LSDR_HIP(hipMalloc((void **)&e->d_tw, kTeN * sizeof(float2)));
   LSDR_HIP(hipMalloc((void **)&e->d_rows, B * e->blocks * kTeN * sizeof(float)));
@@ -182,25 +163,22 @@ static int te_build(lsdr_tune_est *e) {
   }
   LSDR_HIP(hipMemcpy(e->d_tw, tw.data(), kTeN * sizeof(float2), hipMemcpyHostToDevice));
   te_args &A = e->A;
-  A.caps = e->d_caps; A.tw = e->d_tw; A.rows = e->d_rows; A.rec = e->d_rec; A.row_cap = e->blocks;
-  A.in_scale = e->cfg.in_scale == 0.f ? 1.0f : e->cfg.in_scale;
-  A.in_flip = e->cfg.in_format == LSDR_IN_CU16 ? 0x80008000u : 0u;
+  A.caps = e->run.d_caps; A.tw = e->d_tw; A.rows = e->d_rows; A.rec = e->d_rec; A.row_cap = e->blocks;
+  A.in_scale = e->in.in_scale; A.in_flip = e->in.in_flip;
   return LSDR_OK;
 }
 
 int lsdr_tune_est_create(lsdr_ctx *c, const lsdr_tune_est_cfg *cfg, lsdr_tune_est **out) {
   LSDR_ARG(c && cfg && out);
   if (cfg->n_captures < 1) { lsdr_set_error("tune_est: n_captures must be at least 1 (got %d)", cfg->n_captures); return LSDR_E_ARG; }
-  const int kind = te_kind(cfg->in_format);
-  if (kind < 0) { lsdr_set_error("tune_est: in_format %d is none of LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32", cfg->in_format); return LSDR_E_ARG; }
-  if (!std::isfinite(cfg->in_scale) || cfg->in_scale < 0.f) { lsdr_set_error("tune_est: in_scale must be finite and not negative"); return LSDR_E_ARG; }
+  lsdr_in_desc in;
+  LSDR_TRY(lsdr_in_describe("tune_est", cfg->in_format, cfg->in_scale, &in));
   if (cfg->blocks > kTeMaxBlocks) { lsdr_set_error("tune_est: blocks is %u, at most %u", cfg->blocks, kTeMaxBlocks); return LSDR_E_ARG; }
   for (int i = 0; i < 4; ++i)
     if (cfg->reserved[i]) { lsdr_set_error("tune_est: lsdr_tune_est_cfg.reserved must be 0"); return LSDR_E_ARG; }
   lsdr_tune_est *e = new lsdr_tune_est();
-  e->ctx = c; e->cfg = *cfg; e->kind = kind;
+  e->ctx = c; e->cfg = *cfg; e->in = in;
   e->blocks = cfg->blocks ? cfg->blocks : 8u;
-  e->item_bytes = kind == kTeF32 ? 8 : (kind == kTe16 ? 4 : 2);
   const int rc = te_build(e);
   if (rc) { lsdr_tune_est_destroy(e); return rc; }
   *out = e;
@@ -210,45 +188,31 @@ int lsdr_tune_est_create(lsdr_ctx *c, const lsdr_tune_est_cfg *cfg, lsdr_tune_es
 int lsdr_tune_est_run_async(lsdr_tune_est *e, const void *const *iq_dev, const size_t *n_samples) {
   LSDR_ARG(e && iq_dev && n_samples);
   const unsigned B = (unsigned)e->cfg.n_captures;
-  for (unsigned i = 0; i < B; ++i) {
-    if (!iq_dev[i] && n_samples[i]) { lsdr_set_error("tune_est: capture %u has samples and no pointer", i); return LSDR_E_ARG; }
-    if ((size_t)iq_dev[i] % e->item_bytes) { lsdr_set_error("tune_est: capture %u: the pointer is not aligned to the item size (%zu bytes)", i, e->item_bytes); return LSDR_E_ARG; }
-  }
-  if (e->in_flight) { lsdr_set_error("tune_est: a run is in flight (lsdr_tune_est_wait first)"); return LSDR_E_ARG; }
+  LSDR_TRY(lsdr_in_check_each("tune_est", "tune", B, iq_dev, nullptr, n_samples, nullptr, ~(size_t)0, e->in.item_bytes));   // (any length: whole blocks of its front are read)
+  LSDR_TRY(e->run.idle("tune_est", "lsdr_tune_est_wait"));
   lsdr_ctx *c = e->ctx;
   LSDR_HIP(hipSetDevice(c->device));
   unsigned longest = 0;                                      // the grid is sized for it; a shorter capture's workgroups leave at once
   for (unsigned i = 0; i < B; ++i) {
     const size_t whole = n_samples[i] / kTeN;
-    te_cap &cap = e->h_caps[i];
+    te_cap &cap = e->run.h_caps[i];
     cap.in = reinterpret_cast<const unsigned char *>(iq_dev[i]);
     cap.blocks = whole < e->blocks ? (unsigned)whole : e->blocks;
     cap.pad = 0;
     if (cap.blocks > longest) longest = cap.blocks;
   }
-  LSDR_HIP(hipMemcpyAsync(e->d_caps, e->h_caps, B * sizeof(te_cap), hipMemcpyHostToDevice, c->stream));
-  if (longest) {
-    const dim3 grid(longest, B), wg(256);
-    switch (e->kind) {
-      case kTeU8: hipLaunchKernelGGL(k_te_block<kTeU8>, grid, wg, 0, c->stream, e->A); break;
-      case kTeS8: hipLaunchKernelGGL(k_te_block<kTeS8>, grid, wg, 0, c->stream, e->A); break;
-      case kTe16: hipLaunchKernelGGL(k_te_block<kTe16>, grid, wg, 0, c->stream, e->A); break;
-      default: hipLaunchKernelGGL(k_te_block<kTeF32>, grid, wg, 0, c->stream, e->A); break;
-    }
-  }
+  LSDR_TRY(e->run.upload(c->stream));
+  if (longest)
+    in_dispatch(e->in.kind, [&](auto K) { hipLaunchKernelGGL(k_te_block<K()>, dim3(longest, B), dim3(256), 0, c->stream, e->A); });
   hipLaunchKernelGGL(k_te_peak, dim3(B), dim3(256), 0, c->stream, e->A);
   LSDR_HIP(hipGetLastError());
   LSDR_HIP(hipMemcpyAsync(e->h_rec, e->d_rec, B * sizeof(te_record), hipMemcpyDeviceToHost, c->stream));
-  LSDR_HIP(hipEventRecord(e->ev_done, c->stream));
-  e->in_flight = true;
-  return LSDR_OK;
+  return e->run.mark(c->stream);
 }
 
 int lsdr_tune_est_wait(lsdr_tune_est *e, lsdr_tune_estimate *out) {
   LSDR_ARG(e && out);
-  if (!e->in_flight) { lsdr_set_error("tune_est: no run in flight"); return LSDR_E_ARG; }
-  LSDR_HIP(hipEventSynchronize(e->ev_done));
-  e->in_flight = false;
+  LSDR_TRY(e->run.wait("tune_est"));
   memcpy(out, e->h_rec, (size_t)e->cfg.n_captures * sizeof(te_record));
   return LSDR_OK;
 }

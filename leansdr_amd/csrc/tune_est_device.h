@@ -1,9 +1,7 @@
 // leansdr_amd/csrc/tune_est_device.h — the arithmetic of the carrier-offset estimator (lsdr_tune_est, include/lsdr_hip.h; kernels and host
-// side in tune_est.hip).  Everything here is plain C++ on values and arrays, callable from a kernel and from the host: the per-sample
-// conversion, one radix-4 stage of the 4096-point FFT, the order its output comes out in, and the peak's interpolation.
-//
-// The conversion is rxb_device.h's (rxb_in<K>: value = float(item − Z)·in_scale, one rounding per component) restated: that header lives inside
-// cstln_receiver.hip's anonymous namespace with the receiver's types around it and cannot be included from another translation unit.
+// side in tune_est.hip).  Everything here is plain C++ on values and arrays, callable from a kernel and from the host: the fourth
+// power, one radix-4 stage of the 4096-point FFT, the order its output comes out in, and the peak's interpolation.  The samples' conversion
+// is capture_input.h's, as for every object that reads raw captures.
 #ifndef LSDR_TUNE_EST_DEVICE_H
 #define LSDR_TUNE_EST_DEVICE_H
 
@@ -12,44 +10,6 @@
 constexpr unsigned kTeN = 4096;          // samples per block, FFT length
 constexpr unsigned kTeLog4 = 6;          // radix-4 stages
 constexpr unsigned kTeMaxBlocks = 64;
-enum { kTeU8 = 0, kTeS8 = 1, kTe16 = 2, kTeF32 = 3 };                     // one kind per item size (cu16 / cs16 differ in `flip`)
-template <int K> struct te_item { static constexpr unsigned kBytes = K == kTeF32 ? 8u : (K == kTe16 ? 4u : 2u); };
-
-// item `i` of a capture at `src`, converted.  flip: 0x80008000 for cu16 (the bias 32768 is the item's top bit), 0 for cs16.
-template <int K>
-TE_HD float2 te_load(const unsigned char *src, size_t i, float sc, unsigned flip) {
-  if constexpr (K == kTeU8) {
-    const unsigned w = *reinterpret_cast<const unsigned short *>(src + 2 * i);
-    return make_float2((float)((int)(w & 255u) - 128) * sc, (float)((int)(w >> 8) - 128) * sc);
-  } else if constexpr (K == kTeS8) {
-    const unsigned w = *reinterpret_cast<const unsigned short *>(src + 2 * i);
-    return make_float2((float)(int)(signed char)w * sc, (float)(int)(signed char)(w >> 8) * sc);
-  } else if constexpr (K == kTe16) {
-    const unsigned w = *reinterpret_cast<const unsigned *>(src + 4 * i) ^ flip;
-    return make_float2((float)(int)(short)(w & 0xffffu) * sc, (float)((int)w >> 16) * sc);
-  } else {
-    const float2 w = *reinterpret_cast<const float2 *>(src + 8 * i);
-    return make_float2(w.x * sc, w.y * sc);
-  }
-}
-// … the same from the four dwords of one 16-byte load: item q of 16 / kBytes
-template <int K>
-TE_HD float2 te_unpack(const unsigned (&ws)[4], unsigned q, float sc, unsigned flip) {
-  if constexpr (K == kTeU8) {
-    const unsigned w = (ws[q >> 1] >> (16u * (q & 1u))) & 0xffffu;
-    return make_float2((float)((int)(w & 255u) - 128) * sc, (float)((int)(w >> 8) - 128) * sc);
-  } else if constexpr (K == kTeS8) {
-    const unsigned w = ws[q >> 1] >> (16u * (q & 1u));
-    return make_float2((float)(int)(signed char)w * sc, (float)(int)(signed char)(w >> 8) * sc);
-  } else if constexpr (K == kTe16) {
-    const unsigned w = ws[q] ^ flip;
-    return make_float2((float)(int)(short)(w & 0xffffu) * sc, (float)((int)w >> 16) * sc);
-  } else {
-    float re, im;
-    __builtin_memcpy(&re, &ws[2 * q], 4); __builtin_memcpy(&im, &ws[2 * q + 1], 4);
-    return make_float2(re * sc, im * sc);
-  }
-}
 
 TE_HD float2 te_cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 // z ↦ (z·inv)⁴: the fourth power of the normalised sample removes QPSK's modulation (every point of the constellation has the same z⁴)
