@@ -629,6 +629,11 @@ typedef struct lsdr_fir_resampler lsdr_fir_resampler;    /* fir_resampler<cf32,f
 int lsdr_fir_resampler_create(lsdr_ctx *ctx, unsigned ncoeffs, const float *coeffs_host, unsigned interp, lsdr_fir_resampler **f);
 void lsdr_fir_resampler_destroy(lsdr_fir_resampler *f);
 int lsdr_fir_resampler_set_freq(lsdr_fir_resampler *f, float freq);
+/* *consumed = min((n_in·interp − ncoeffs)/interp, n_in − latency, cap_out/interp), latency = (ncoeffs + interp)/interp;
+ * *produced = *consumed·interp.  The n_in − latency bound is the one place where the block deliberately departs from the
+ * reference: it changes nothing unless interp divides ncoeffs, where the reference's last output group reads in[n_in] — a pipe
+ * slot nobody has written, so its value there is arbitrary.  Here no read leaves in[0 … n_in); the held-back sample is consumed,
+ * and its group produced, by the next call.  Carry the unconsumed input as with every other block. */
 int lsdr_fir_resampler_run(lsdr_fir_resampler *f, const lsdr_cf32 *in, size_t n_in, lsdr_cf32 *out, size_t cap_out, size_t *consumed,
                            size_t *produced);
 typedef struct lsdr_simple_agc lsdr_simple_agc;          /* simple_agc<f32>, sdr.h:238-274 (power estimate carried) */

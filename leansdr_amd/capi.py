@@ -668,6 +668,16 @@ class Ctx:
         din.free(); dout.free()
         return out
 
+    def cconverter_int(self, in_format, iq):
+        """iq: interleaved re, im of int8 (IN_CS8), uint16 (IN_CU16) or int16 (IN_CS16)."""
+        iq = np.ascontiguousarray(iq, {IN_CS8: np.int8, IN_CU16: np.uint16, IN_CS16: np.int16}[in_format]).reshape(-1, 2)
+        din = self.upload(iq)
+        dout = self.alloc(max(8, len(iq) * 8))
+        check(lib.lsdr_cconverter_int_run(self.h, in_format, din.ptr, len(iq), dout.ptr))
+        out = self.download(dout, np.complex64, len(iq))
+        din.free(); dout.free()
+        return out
+
     def scaler(self, scale, x):
         x = np.ascontiguousarray(x, np.complex64)
         din = self.upload(x)

@@ -396,10 +396,15 @@ int lsdr_fir_resampler_run(lsdr_fir_resampler *f, const lsdr_cf32 *in, size_t n_
   if (n_in < f->ncoeffs) return LSDR_OK;                                    // dsp.h:307
   if (n_in * f->interp < f->ncoeffs) return LSDR_OK;                        // dsp.h:318
   size_t count = (n_in * f->interp - f->ncoeffs) / f->interp;
+  // Output group m reads in[latency + m] (k_fir_resample), so count ≤ n_in − latency keeps every read inside the caller's
+  // n_in samples.  Equal to the reference's count unless interp divides ncoeffs, where the reference's last group reads
+  // in[n_in], a pipe slot nobody has written: that one group is held back and produced by the next call (include/lsdr_hip.h).
+  const unsigned latency = (f->ncoeffs + f->interp) / f->interp;
+  if (n_in <= latency) return LSDR_OK;
+  if (count > n_in - latency) count = n_in - latency;
   if (count > cap_out / f->interp) count = cap_out / f->interp;
   if (!count) return LSDR_OK;
   LSDR_ARG(in && out);
-  const unsigned latency = (f->ncoeffs + f->interp) / f->interp;
   const unsigned long long nout = (unsigned long long)count * f->interp;
   hipLaunchKernelGGL(k_fir_resample, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, f->ctx->stream, (const float2 *)in,
                      (const float2 *)f->d_sc, f->ncoeffs, f->interp, latency, nout, (float2 *)out);

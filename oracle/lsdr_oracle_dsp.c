@@ -163,8 +163,14 @@ size_t lo_fir_resampler(unsigned ncoeffs, const lo_cf32 *sc, int interp,
   if (n_in < ncoeffs) return 0;
   if (n_in * interp < ncoeffs) return 0;
   size_t count = (n_in * interp - ncoeffs) / interp;
-  if (count > cap / interp) count = cap / interp;
   int latency = (ncoeffs + interp) / interp;
+  /* The one deliberate departure from the reference: output group m reads in[latency + m], so count is bounded by
+   * n_in - latency.  That is the reference's count whenever interp does not divide ncoeffs (both are
+   * n_in - ceil(ncoeffs/interp)) and one less when it does, where the reference's last group reads in[n_in], a pipe
+   * slot nobody has written.  The held-back sample is produced by the next call, from real data. */
+  if (n_in <= (size_t)latency) return 0;
+  if (count > n_in - latency) count = n_in - latency;
+  if (count > cap / interp) count = cap / interp;
   lo_cf32 *pout = out;
   for (size_t m = 0; m < count; ++m) {
     const lo_cf32 *pin = in + latency + m;

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 from conftest import gold, bits_equal, iq16_to_cf32, GOLD
 import pyoracle as po
+import modcod_common as mc
 
 
 def sha(a):
@@ -118,10 +119,7 @@ def rx_input(oracle, g, src, limit):
     return x[:limit] if limit else x
 
 
-def state_vec(st):
-    d = st.as_dict()
-    keys = ["mu", "phase", "freqw", "agc_gain", "est_insp", "est_sp", "est_ep", "freq_tap", "min_freqw", "max_freqw"]
-    return np.array([d[k] for k in keys] + d["hist"], np.float32), int(d["meas_count"])
+state_vec = mc.state_vec     # (lives beside the digests that hash it; the GPU receiver tests import it from here)
 
 
 def check_rx_against_golden(r, g, tag):
@@ -193,6 +191,48 @@ def test_spectrum(oracle):
     assert bits_equal(oracle.spectrum(x, 4096, 0.5), s["d4096_k05"])
     assert bits_equal(oracle.spectrum(x, 3000, 0.1), s["d3000_k01"])
     assert s["d4096_k05"].shape == (8, 1024)
+
+
+_modcod = {}
+
+
+def modcod_gold():
+    if not _modcod:
+        _modcod.update(gold("modcod.npz"))     # read once: 92 cases share it
+    return _modcod
+
+
+@pytest.mark.parametrize("case", mc.RX_SWEEP, ids=mc.case_id)
+def test_cstln_receiver_modcods(oracle, case):
+    """Every constellation x receiver setting of modcod_common.py against the reference's recorded hashes (tests/golden/modcod.npz):
+    pins the oracle where the reference is not built — the GPU machine included, whose tests compare with this oracle."""
+    g = modcod_gold()
+    c, r, v, s = case
+    x = mc.rx_input(oracle, c, r, v, s)
+    d = mc.rx_digest(mc.oracle_rx(oracle, case, gold("tables.npz")["rrc_rx"] if s == 2 else None), x)
+    row = mc.RX_SWEEP.index(case)
+    assert g["rx_ids"][row] == mc.case_id(case)
+    want_n, want = g["rx_n"][row], g["rx_sha"][row]
+    assert int(want_n[0]) == len(x) and bytes(want[0]) == bytes(d["sha"][0]), \
+        "the INPUT differs from the one the golden was made from (numpy generator or transmit chain changed): regenerate modcod.npz"
+    assert d["n"].tolist() == want_n.tolist()
+    for k, name in enumerate(mc.DIGEST_FIELDS):
+        assert bytes(d["sha"][k]) == bytes(want[k]), name
+
+
+def test_tx_blocks_modcods(oracle):
+    """cstln_transmitter, dvb_convol and fir_resampler at every pair / shape of modcod_common.py against the reference's hashes."""
+    g = modcod_gold()
+    assert g["tx_ids"].tolist() == [list(p) for p in mc.TX_PAIRS] and g["convol_ids"].tolist() == [list(p) for p in mc.CONVOL_PAIRS]
+    assert g["resampler_ids"].tolist() == [[n, i] for n, i, _ in mc.RESAMPLER_CASES + mc.RESAMPLER_DIVIDING]
+    for k, (c, r) in enumerate(mc.TX_PAIRS):
+        assert mc.sha(oracle.cstln_transmitter(mc.tx_symbols(c), c, r)) == bytes(g["tx_sha"][k]), (c, r)
+    for k, (rate, bps) in enumerate(mc.CONVOL_PAIRS):
+        assert mc.sha(oracle.dvb_convol(mc.convol_input(), rate, bps)[0]) == bytes(g["convol_sha"][k]), (rate, bps)
+    for k, (n, i, f) in enumerate(mc.RESAMPLER_CASES + mc.RESAMPLER_DIVIDING):
+        y, cons = oracle.fir_resampler(mc.resampler_coeffs(n), i, mc.resampler_input(), f)
+        assert cons == mc.RESAMPLER_N_IN - (n + i) // i        # never more than n_in - latency: no read past the input
+        assert len(y) == int(g["resampler_n"][k]) and mc.sha(y) == bytes(g["resampler_sha"][k]), (n, i)
 
 
 def rotator_input():

@@ -3,8 +3,9 @@
 the committed goldens (test_oracle_golden.py) cover that case."""
 import numpy as np
 import pytest
-from conftest import bits_equal
+from conftest import bits_equal, gold
 import pyoracle as po
+import modcod_common as mc
 
 
 @pytest.fixture(scope="module")
@@ -115,6 +116,76 @@ def test_cstln_receiver_fir_sampler(oracle, ref, sig):
     rr1 = oracle.rrc(40, np.float32(0.25), np.float32(0.35))
     p = po.rx_params(sampler=2, coeffs=rr1, subsampling=1, cstln=1, omega=4.0, meas_decimation=4096)
     same_rx(oracle.rx(p, sig), ref.rx(p, sig))
+
+
+@pytest.mark.parametrize("case", mc.RX_SWEEP, ids=mc.case_id)
+def test_cstln_receiver_modcods(oracle, ref, case):
+    """Every constellation (with one code rate each) x five settings x nearest / linear, and the FIR sampler twice: what the GPU's exact
+    receivers are held to (test_gpu_rx_modcods.py) is the compiled reference's output, bit for bit — and the inputs do exercise what
+    they are meant to: the whole symbol table, and the !allow_drift reset of the frequency limits (sdr.h:895-898)."""
+    c, r, v, s = case
+    rrc = gold("tables.npz")["rrc_rx"] if s == 2 else None
+    x = mc.rx_input(oracle, c, r, v, s)
+    a = mc.oracle_rx(oracle, case, rrc)
+    same_rx(a, ref.rx(po.rx_params(**mc.rx_kwargs(c, r, v, s, rrc)), x))
+    assert len(a["sym"]) > 4000 and len(a["freq"]) >= 14
+    distinct = len(np.unique(a["sym"]["symbol"]))
+    n = mc.NSYMBOLS[c]
+    assert distinct >= {64: 48, 256: 128}.get(n, n), distinct
+    if v == "clamp" and c in (1, 2, 3, 4):
+        assert (a["freq"][1:] == 0).any()
+    if v == "sps3_loud_drift":
+        assert np.abs(x.view(np.float32)).max() > 127
+
+
+@pytest.mark.parametrize("cstln,rate", mc.TX_PAIRS)
+def test_cstln_transmitter(oracle, ref, cstln, rate):
+    sym = mc.tx_symbols(cstln)
+    assert bits_equal(oracle.cstln_transmitter(sym, cstln, rate), ref.cstln_transmitter(sym, cstln, rate))
+
+
+@pytest.mark.parametrize("rate,bps", mc.CONVOL_PAIRS)
+def test_dvb_convol(oracle, ref, rate, bps):
+    """Every code rate with every symbol width its puncturing period allows."""
+    data = mc.convol_input()
+    a, cons = oracle.dvb_convol(data, rate, bps)
+    bi, bo = mc.FEC_BITS[rate]
+    assert cons == len(data) and len(a) == len(data) * 8 // bi * bo // bps
+    assert bits_equal(a, ref.dvb_convol(data, rate, bps))
+
+
+def test_simple_agc_before_the_first_estimate(oracle, ref):
+    """Leading all-zero chunks: no estimate, gain 0; the first non-zero chunk seeds it (sdr.h:253-273)."""
+    x = mc.resampler_input(128 * 70)
+    x[:3 * 128] = 0
+    ya, ea = oracle.simple_agc(x, 0.7, 0.01)
+    yb, eb = ref.simple_agc(x, 0.7, 0.01)
+    assert bits_equal(ya, yb) and ea == eb and not ya[:3 * 128].any() and ya[3 * 128:].all()
+
+
+@pytest.mark.parametrize("ncoeffs,interp,freq", mc.RESAMPLER_CASES)
+def test_fir_resampler_shapes(oracle, ref, ncoeffs, interp, freq):
+    co, x = mc.resampler_coeffs(ncoeffs), mc.resampler_input()
+    a, cons = oracle.fir_resampler(co, interp, x, freq)
+    assert cons == len(x) - -(-ncoeffs // interp) and len(a) == cons * interp
+    assert bits_equal(a, ref.fir_resampler(co, interp, x, freq))
+
+
+@pytest.mark.parametrize("ncoeffs,interp,freq", mc.RESAMPLER_DIVIDING)
+def test_fir_resampler_interp_divides_ncoeffs(oracle, ref, ncoeffs, interp, freq):
+    """Where interp divides ncoeffs the reference's last output group reads in[n_in], a pipe slot nobody has written.  The oracle
+    (and the GPU block) hold that one input sample back: every other output is the reference's, no read leaves the input (a NaN
+    behind it does not show), and the held-back group comes out of the next call, from real data."""
+    co, x = mc.resampler_coeffs(ncoeffs), mc.resampler_input()
+    padded = np.concatenate([x, np.array([np.nan + 1j * np.nan], np.complex64)])
+    a, cons = oracle.fir_resampler(co, interp, padded[:len(x)], freq)
+    b = ref.fir_resampler(co, interp, x, freq)
+    assert cons == len(x) - ncoeffs // interp - 1 and len(a) == cons * interp and len(b) == len(a) + interp
+    assert bits_equal(a, b[:len(a)]) and not np.isnan(a.view(np.float32)).any()
+    more = np.concatenate([x, mc.resampler_input(64)[:50]])
+    whole, _ = oracle.fir_resampler(co, interp, more, freq)
+    nxt, _ = oracle.fir_resampler(co, interp, more[cons:], freq)
+    assert bits_equal(np.concatenate([a, nxt]), whole)
 
 
 def test_rotator(oracle, ref, sig):
