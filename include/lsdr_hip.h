@@ -971,6 +971,74 @@ void lsdr_tune_est_destroy(lsdr_tune_est *e);
 int lsdr_tune_est_run_async(lsdr_tune_est *e, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
 int lsdr_tune_est_wait(lsdr_tune_est *e, lsdr_tune_estimate *out /* [B] */);
 
+/* ------------------------------------------------------------ per-capture samples per symbol, estimated (PSK, RRC shaping)
+ * The number every batch object wants at create (lsdr_capture_batch_cfg.omega, lsdr_hs_batch_cfg.omega, lsdr_resample_design's omega),
+ * from the raw capture: a job of recordings is not all at one symbol rate, and the reference has no block for this (--sr is mandatory).
+ * It runs in front of the decoders, before or beside lsdr_tune_est, and touches none of their kernels.
+ *
+ * THE ESTIMATOR.  The squared magnitude of a root-raised-cosine PSK signal has a spectral line at the symbol rate, wherever the carrier
+ * is.  For one capture of n items let M = min(blocks, n / 4096) whole blocks of N = 4096 samples, from the capture's first sample:
+ *   1 convert the samples as the capture batch's loads do: float(item − Z)·in_scale (lsdr_capture_input_cfg);
+ *   2 per block s = mean |z|² and p[n] = |z[n]|²/s − 1; a block with s = 0 contributes zeros to every sum below and is not counted in M₁;
+ *   3 X = FFT_N(p + 0j), rectangular window (lsdr_tune_est's transform); P[k] += |X[k]|², summed in block order;
+ *   4 in the same pass c₁ += Σ_{n=1…N−1} z[n]·conj(z[n−1]) / s, the sum inside the block in a fixed order; R = |c₁| / (M₁·(N − 1)), M₁ the
+ *     number of nonzero blocks: the normalised lag-one autocorrelation magnitude, which no carrier offset moves;
+ *   5 the bins searched are k ∈ [k_lo, N/2], k_lo = max(2, ⌊N/omega_max⌋) (P is symmetric, and the low bins hold the level's slow content;
+ *     with omega_max < 2, where that lies behind N/2 and only candidate b below is admissible, k_lo = max(2, ⌊N·(1 − 1/omega_min)⌋));
+ *     floor = mean of P over them; k0 = their first arg-max, c = P[k0]; l′ = max(P[k0−1] − floor, 0), r′ = max(P[k0+1] − floor, 0);
+ *     m = sqrt(max(l′, r′)/c), δ = ±m/(1 + m), + when r′ ≥ l′; line = (k0 + δ)/N, folded into (0, 0.5] by line ↦ 1 − line where it
+ *     exceeds 0.5;
+ *   6 the candidates are omega_a = 1/line (≥ 2) and omega_b = 1/(1 − line) (in [1, 2]): the line of omega < 2 aliases onto that of some
+ *     omega ≥ 2 (1.2 and 6 both put it at 1/6 cycle per sample).  A candidate outside [omega_min, omega_max] is dropped.  If both remain,
+ *     a is chosen when |R − |sinc(line)|| < |R − |sinc(1 − line)||, else b, with sinc(x) = sin(πx)/(πx).  omega is the chosen candidate,
+ *     other the other one, or 0 if it was dropped; ambiguous = 1 when both were admissible and line > 0.4 (omega in about (1.67, 2.5),
+ *     where the two converge and R cannot be trusted to tell them apart);
+ *   7 quality = c / floor;
+ *   8 the record is all zeros when M = 0, when c = 0, or when no candidate is admissible.
+ * LIMITS: QPSK/PSK with RRC shaping — the line's height follows the roll-off, and a roll-off near 0 has no line.  The estimate is taken
+ * from the capture's start.  A periodic interferer in the magnitude can win the peak.  omega within [omega_min, omega_max] ⊆ [1.016, 64].
+ * ACCURACY, measured on synthetic DVB-S captures (roll-off 0.35; tests/test_rate_est_abi.py, tests/test_gpu_rate_est.py; DESIGN.md
+ * §4.11) with 64 blocks, at 6/5, 3/2, 3, 4, 8 and 12 samples per symbol, noise 7.5 and 18 on the cu8 scale, every capture 0.03 cycles
+ * per sample off tune: |omega/true − 1| ≤ 3.0e-5; the tests hold it to 2.5e-4, a quarter of the 1e-3 by which the reference's --sr may be
+ * off with its TS unchanged.  QUALITY reads as the line's height over the mean of the searched bins: 47 … 187 on those captures, at most
+ * 1.6 on Gaussian noise alone with 64 blocks (2.3 with 16); a capture below about 10 has no line worth believing.
+ * A record is a pure function of the capture's own converted samples: no atomics, every sum in a fixed order — bit for bit the same alone,
+ * in any batch and at any place in it, run twice, and in every format that converts to the same floats.
+ * run_async queues everything on the context's stream (behind lsdr_memcpy_h2d on that context) and returns: one launch over all blocks of
+ * all captures, one over the captures, the records' copy to pinned memory; no host read in between.  wait is one event synchronisation and
+ * the read of B records.  One run in flight per object.
+ * iq_dev: HOST array of B DEVICE pointers, each aligned to its item size (2, 2, 4, 4, 8 bytes for cu8, cs8, cu16, cs16, cf32; a 16-byte
+ * aligned capture is read by 16-byte loads), NULL only where n_samples[i] is 0.  Nothing behind block M − 1 of a capture is read.
+ * LSDR_E_ARG, with a message naming rate_est, the object (if any) left usable: n_captures < 1 (or above 65535), in_format outside the five
+ * LSDR_IN_*, in_scale negative or not finite, blocks > 256, omega_min or omega_max outside [1.016, 64] or omega_min > omega_max, nonzero
+ * reserved; a misaligned pointer, samples without a pointer, run_async with a run in flight, wait with none. */
+typedef struct lsdr_rate_est lsdr_rate_est;
+typedef struct {
+  int n_captures;      /* B */
+  int in_format;       /* LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32 */
+  float in_scale;      /* as lsdr_tune_est_cfg.in_scale: 0 or 1 = none (the normalisation makes the estimate independent of it, up to rounding) */
+  unsigned blocks;     /* blocks of 4096 samples per capture, at most 256; 0 = 64 */
+  float omega_min;     /* the smallest samples per symbol admitted; 0 = 1.016 */
+  float omega_max;     /* the largest; 0 = 64 */
+  int reserved[2];     /* 0 */
+} lsdr_rate_est_cfg;   /* 32 bytes */
+typedef struct {
+  float omega;         /* samples per symbol: what the batch objects' omega takes; 0 = nothing found (the record is all zeros) */
+  float other;         /* the candidate that was not chosen; 0 = it was not admissible */
+  float line;          /* the line's frequency, cycles per sample, in (0, 0.5] */
+  float quality;       /* power[1] / floor */
+  float corr;          /* R */
+  uint32_t bin;        /* k0, k_lo … 2048 */
+  uint32_t blocks;     /* M: the blocks that were used */
+  uint32_t ambiguous;  /* 1: both candidates admissible and line > 0.4 */
+  float power[3];      /* P at k0 − 1, k0, k0 + 1 */
+  float floor;         /* mean of P over the searched bins */
+} lsdr_rate_estimate;  /* 48 bytes */
+int lsdr_rate_est_create(lsdr_ctx *ctx, const lsdr_rate_est_cfg *cfg, lsdr_rate_est **e);
+void lsdr_rate_est_destroy(lsdr_rate_est *e);
+int lsdr_rate_est_run_async(lsdr_rate_est *e, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
+int lsdr_rate_est_wait(lsdr_rate_est *e, lsdr_rate_estimate *out /* [B] */);
+
 /* ------------------------------------------------------------ resample batch: --derotate --resample for many captures
  * The batch decoders take omega = Fs/Fm in [1, 8] and have no filter in front of the receiver; a recording from an ordinary SDR is wider
  * (2.4 MS/s around a 250 kS/s carrier is omega 9.6).  leandvb puts rotator<f32> (--derotate, leandvb.cc:310-318, sdr.h:1226-1259) and a

@@ -394,6 +394,28 @@ _sig("lsdr_tune_est_run_async", C.c_int, [vp, vp, psz])
 _sig("lsdr_tune_est_wait", C.c_int, [vp, C.POINTER(TuneEstimate)])
 
 
+class RateEstCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("in_format", C.c_int), ("in_scale", C.c_float), ("blocks", C.c_uint), ("omega_min", C.c_float),
+                ("omega_max", C.c_float), ("reserved", C.c_int * 2)]
+
+
+class RateEstimate(C.Structure):
+    """lsdr_rate_estimate: one capture's estimated samples per symbol."""
+    _fields_ = [("omega", C.c_float), ("other", C.c_float), ("line", C.c_float), ("quality", C.c_float), ("corr", C.c_float),
+                ("bin", C.c_uint32), ("blocks", C.c_uint32), ("ambiguous", C.c_uint32), ("power", C.c_float * 3), ("floor", C.c_float)]
+
+    def as_dict(self):
+        return dict(omega=float(self.omega), other=float(self.other), line=float(self.line), quality=float(self.quality),
+                    corr=float(self.corr), bin=int(self.bin), blocks=int(self.blocks), ambiguous=int(self.ambiguous),
+                    power=[float(v) for v in self.power], floor=float(self.floor))
+
+
+_sig("lsdr_rate_est_create", C.c_int, [vp, C.POINTER(RateEstCfg), C.POINTER(vp)])
+_sig("lsdr_rate_est_destroy", None, [vp])
+_sig("lsdr_rate_est_run_async", C.c_int, [vp, vp, psz])
+_sig("lsdr_rate_est_wait", C.c_int, [vp, C.POINTER(RateEstimate)])
+
+
 class ResampleBatchCfg(C.Structure):
     _fields_ = [("n_captures", C.c_int), ("max_samples", C.c_size_t), ("in_format", C.c_int), ("in_scale", C.c_float), ("ncoeffs", C.c_uint),
                 ("coeffs_host", vp), ("decim", C.c_uint), ("reserved", C.c_int * 6)]
@@ -436,6 +458,10 @@ _sig("lsdr_spectrum_batch_rows_dev", vp, [vp, C.c_int])
 #: decode_estimated's default threshold on `quality`: the geometric mean of what Gaussian noise alone reaches (3.1) and the weakest of the
 #: test captures (347), rounded
 TUNE_MIN_QUALITY = 30.0
+
+#: group_by_omega's default threshold on a rate estimate's `quality`: the geometric mean of what Gaussian noise alone reaches (2.3 with 16
+#: blocks, 1.6 with 64) and the weakest of the test captures (47), rounded
+RATE_MIN_QUALITY = 10.0
 
 #: every symbol include/lsdr_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [n for n in dir(lib) if n.startswith("lsdr_")]
@@ -972,6 +998,67 @@ class TuneEstimator:
         """One run, synchronously: [dict(tune, quality, bin, blocks, power [l, c, r], mean_power)] per capture."""
         self.run_async(iq_ptrs, n_samples)
         return self.wait()
+
+
+class RateEstimator:
+    """lsdr_rate_est: the samples per symbol of each of n_captures captures, estimated from the raw samples (RRC-shaped PSK: the spectral
+    line of the squared magnitude, over the first `blocks` blocks of 4096 samples) — the omega the batch objects want at construction."""
+
+    def __init__(self, ctx, n_captures, in_format=IN_CU8, in_scale=0.0, blocks=64, omega_min=0.0, omega_max=0.0):
+        self.ctx, self.n, self.h = ctx, int(n_captures), None
+        cfg = RateEstCfg()
+        cfg.n_captures, cfg.in_format, cfg.in_scale, cfg.blocks = self.n, int(in_format), float(in_scale), int(blocks)
+        cfg.omega_min, cfg.omega_max = float(omega_min), float(omega_max)
+        h = vp()
+        check(lib.lsdr_rate_est_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self._out = (RateEstimate * self.n)()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_rate_est_destroy(self.h)
+            self.h = None
+
+    def _args(self, iq_ptrs, n_samples):
+        n = [int(v) for v in n_samples]
+        if len(n) != self.n or len(iq_ptrs) != self.n:
+            raise LsdrError(f"rate estimator: {len(iq_ptrs)} pointers and {len(n)} lengths for {self.n} captures")
+        return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs]), (c_sz * self.n)(*n)
+
+    def run_async(self, iq_ptrs, n_samples):
+        """Queues the estimate of every capture's first n_samples[i] items; a pointer may be None where the length is 0."""
+        check(lib.lsdr_rate_est_run_async(self.h, *self._args(iq_ptrs, n_samples)))
+
+    def wait(self):
+        check(lib.lsdr_rate_est_wait(self.h, self._out))
+        return [r.as_dict() for r in self._out]
+
+    def estimate(self, iq_ptrs, n_samples):
+        """One run, synchronously: [dict(omega, other, line, quality, corr, bin, blocks, ambiguous, power [l, c, r], floor)] per capture."""
+        self.run_async(iq_ptrs, n_samples)
+        return self.wait()
+
+
+def group_by_omega(estimates, rtol=1e-3, min_quality=RATE_MIN_QUALITY):
+    """The captures of a job sorted by rate: ([(omega, [capture indices])], [indices left out]) from RateEstimator's records.  Taken in
+    ascending omega, a record joins the group whose first member it is within rtol of, and a group's omega is the median of its members'
+    — the caller makes one CaptureBatch / HsBatch / ResampledDecoder per group.  Left out, in their own list: records below min_quality
+    (all-zero records among them) and `ambiguous` ones, whose two candidates are for the caller to try."""
+    good = sorted((i for i, e in enumerate(estimates) if e["quality"] >= min_quality and not e["ambiguous"] and e["omega"] > 0),
+                  key=lambda i: (estimates[i]["omega"], i))
+    left = [i for i in range(len(estimates)) if i not in set(good)]
+    groups = []
+    for i in good:
+        if groups and estimates[i]["omega"] <= estimates[groups[-1][0]]["omega"] * (1.0 + rtol):
+            groups[-1].append(i)
+        else:
+            groups.append([i])
+    out = []
+    for g in groups:
+        om = sorted(estimates[i]["omega"] for i in g)
+        mid = len(om) // 2
+        out.append((om[mid] if len(om) % 2 else 0.5 * (om[mid - 1] + om[mid]), sorted(g)))
+    return out, left
 
 
 class _TailBatch:

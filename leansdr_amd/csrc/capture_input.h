@@ -1,6 +1,6 @@
 // leansdr_amd/csrc/capture_input.h — the one place that knows the raw captures' sample formats (LSDR_IN_*, include/lsdr_hip.h), for every
 // object that reads captures on the device: lsdr_capture_batch / lsdr_hs_batch (host side only: rxb_host.h, hsb_host.h, capture_batch.hip),
-// lsdr_tune_est, lsdr_resample_batch, lsdr_spectrum_batch (host side and kernels).  Plain C++ on values, callable from a kernel and from
+// lsdr_tune_est, lsdr_rate_est, lsdr_resample_batch, lsdr_spectrum_batch (host side and kernels).  Plain C++ on values, callable from a kernel and from
 // the host:
 //   the kinds, in_item / in_load / in_unpack / in_piece   an item converted: value = float(item − Z)·in_scale, one rounding per component
 //   lsdr_in_describe, lsdr_in_check_each                   an object's format and scale at create, a run's per-capture arguments
@@ -125,7 +125,7 @@ inline int lsdr_in_check_each(const char *who, const char *tune_word, unsigned B
 }
 
 // The per-capture records of a run (pinned, and the device copy the kernels read), the event behind the run's last operation, and the flag
-// between run_async and wait — of lsdr_tune_est, lsdr_resample_batch and lsdr_spectrum_batch.  The device is the caller's to set.
+// between run_async and wait — of lsdr_tune_est, lsdr_rate_est, lsdr_resample_batch and lsdr_spectrum_batch.  The device is the caller's to set.
 template <class Cap>
 struct in_run {
   Cap *h_caps = nullptr, *d_caps = nullptr;
