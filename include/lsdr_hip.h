@@ -1039,6 +1039,69 @@ void lsdr_rate_est_destroy(lsdr_rate_est *e);
 int lsdr_rate_est_run_async(lsdr_rate_est *e, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
 int lsdr_rate_est_wait(lsdr_rate_est *e, lsdr_rate_estimate *out /* [B] */);
 
+/* ------------------------------------------------------------ per-stream code rate, estimated from the hard symbols (QPSK)
+ * The last constructor argument of the batch decoders that has to be known per capture: lsdr_capture_batch_cfg.fec, leandvb's mandatory
+ * --cr.  A capture decoded at the wrong rate gives nothing back and says nothing about why.  The measurement is the reference's own:
+ * deconvol_sync inverts the convolutional code with two different polynomials per output bit (deconv[b], deconv2[b], dvb.h:225-265) and
+ * readerrors() (dvb.h:391-412) counts how often they disagree — --fastlock chooses among the four alignments by that count and gives an
+ * alignment up above 1/3 (dvb.h:449-453).  deconv[b] ^ deconv2[b] is a parity check of the punctured code: 0 on every error-free code word
+ * of the right rate at the right alignment and symbol phase, a coin flip on anything else.  This object sweeps it over all five rates,
+ * every symbol phase of the puncturing pattern and the four alignments, for many streams at once.  It needs no tune, no MPEG framing and
+ * no second decode: the receivers' QPSK decisions do not depend on fec, so one front-end pass feeds every hypothesis.
+ *
+ * THE DEFINITION.  All integers: every implementation agrees bit for bit.  One stream has n hard symbols s[0 … n), each `symbol & 3` as
+ * deconvol_sync reads them (dvb.h:373,396); the first min(n, max_symbols) are scored.  A hypothesis is (rate r, alignment a, skip k):
+ *   r in {1/2, 2/3, 3/4, 5/6, 7/8}; 2/3 is handled as 4/6 (dvb.h:491-495) and reported as LSDR_FEC23;
+ *   a in 0 … 3: the lut of init_syncs (dvb.h:308-360);
+ *   k in [0, punctweight/2): 1, 3, 2, 3, 4 values for the five rates — 13 (rate, skip) pairs, 52 hypotheses.
+ * E(r,a,k) is what readerrors() of a freshly constructed deconvol_sync of rate r on alignment a counts over all complete refills of
+ * s[k … n): R = (n − k >= 32) ? (n − k − 32)/(punctweight/2) + 1 : 0 refills; refill q looks at the 32 symbols that end in front of
+ * symbol k + 32 + q·punctweight/2 (the newest in the window's low bits) and adds, for b = punctperiod − 1 … 0,
+ * parity(w & deconv[b]) != parity(w & deconv2[b]).  C(r,a,k) = R·punctperiod.
+ * Per rate the best hypothesis is the first, a outer and k inner, with the smallest E/C; fractions are compared exactly
+ * (E1·C2 < E2·C1 in 64-bit integers) and a hypothesis with C = 0 never wins.  Per stream the winner is the first rate, in the order
+ * above, with the smallest best fraction; locked = (C > 0 and 3·E <= C), the reference's own criterion; ambiguous = a second rate also
+ * satisfies it.  No symbols, or fewer than 32: the record is all zeros with fec = −1.
+ * WHAT THE FRACTION MEANS.  The check polynomials have w = 10 / 12 / 18 / 24 / 32 taps (1/2 … 7/8); at a channel bit error rate q the right
+ * hypothesis reads (1 − (1 − 2q)^w)/2 and every wrong one about 1/2.  It stays under 1/3 up to q of about 5 % at rate 1/2 and 1.7 % at 7/8:
+ * exactly where leandvb --fastlock itself holds an alignment.  Measured (tests/test_fec_est_host.py): synthetic captures at
+ * 1.2 samples per symbol, noise 7.5 on the cu8 scale, 4096 symbols: 0.044 … 0.137 for the transmitted rate, at least 0.449 for every
+ * other; uniformly random symbols 0.462.
+ * LIMITS: QPSK only.  Hard decisions only: a weak capture that needs --viterbi reads near 1/2 for every rate and comes back locked = 0.
+ * The estimate rests on the first max_symbols symbols, acquisition included.  The checks have even weight: a stretch of constant symbols
+ * satisfies those of every rate, so a stream that is partly constant reads below 1/2 for the wrong rates too (`ambiguous` says so).
+ * run_async queues everything on the context's stream and returns: a memset of the counters, one launch over all tiles of all streams,
+ * one over the streams, the records' copy to pinned memory; nothing is synchronised or read on the host in between.  wait is one event
+ * synchronisation and the read of n_streams records.  One run in flight per object.
+ * LSDR_E_ARG, with a message naming fec_est, the object (if any) left usable: n_streams < 1 (or above 65535), max_symbols 0 (or above
+ * 2^28), an unknown in_format, nonzero reserved; symbols without a pointer, a packed or soft pointer that is not 4-byte aligned,
+ * run_async with a run in flight, wait with none. */
+enum { LSDR_HSYM_PACKED2 = 0,   /* 16 per uint32, MSB first: lsdr_capture_batch_words_dev, LSDR_SYM_HARD2 */
+       LSDR_HSYM_U8 = 1,        /* one per byte: lsdr_hs_batch_symbols_dev, lsdr_fastqpsk_run */
+       LSDR_HSYM_SOFT = 2 };    /* lsdr_softsymbol, `symbol & 3`: lsdr_capture_batch_soft_dev, lsdr_rx_run */
+typedef struct lsdr_fec_est lsdr_fec_est;
+typedef struct { int n_streams; size_t max_symbols; int in_format; int reserved[5]; } lsdr_fec_est_cfg;
+typedef struct { uint64_t errors, checks; uint32_t sync, skip; } lsdr_fec_est_score;   /* 24 bytes */
+typedef struct {
+  int32_t fec;                 /* LSDR_FEC12 / 23 / 34 / 56 / 78; −1: nothing scored */
+  uint32_t locked, ambiguous, sync, skip, pad;
+  uint64_t symbols;            /* symbols scored: min(n, max_symbols) */
+  float error_rate, runner_up; /* (float)((double)E/C) of the winner and of the best other rate */
+  lsdr_fec_est_score score[5]; /* per rate, in the order 1/2, 2/3, 3/4, 5/6, 7/8: its best hypothesis */
+} lsdr_fec_estimate;           /* 160 bytes */
+int lsdr_fec_est_create(lsdr_ctx*, const lsdr_fec_est_cfg*, lsdr_fec_est**);
+void lsdr_fec_est_destroy(lsdr_fec_est*);
+/* the symbols per workgroup tile: the lengths at which the score kernel changes its path are multiples of it */
+unsigned lsdr_fec_est_tile(const lsdr_fec_est*);
+/* sym_dev: HOST array of DEVICE pointers (may be NULL where n is 0); sym_offset (may be NULL: zeros): the first symbol's position in the
+ * stream that starts at sym_dev[i] (packed streams: any value; the others: added to the pointer); n[i] symbols from there, of which the first
+ * min(n[i], max_symbols) are scored.  Queues everything on the context's stream and returns. */
+int lsdr_fec_est_run_async(lsdr_fec_est*, const void *const *sym_dev, const uint64_t *sym_offset, const uint64_t *n);
+int lsdr_fec_est_wait(lsdr_fec_est*, lsdr_fec_estimate *out /* [n_streams] */);
+/* host only, no context: the polynomials a rate is scored with (what lsdr_deconv_create computes); returns punctperiod, *punctweight
+ * (0, with a message, for a rate that is none of the five) */
+int lsdr_fec_est_polys(int rate, uint64_t deconv[8], uint64_t deconv2[8], int *punctweight);
+
 /* ------------------------------------------------------------ resample batch: --derotate --resample for many captures
  * The batch decoders take omega = Fs/Fm in [1, 8] and have no filter in front of the receiver; a recording from an ordinary SDR is wider
  * (2.4 MS/s around a 250 kS/s carrier is omega 9.6).  leandvb puts rotator<f32> (--derotate, leandvb.cc:310-318, sdr.h:1226-1259) and a

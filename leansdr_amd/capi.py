@@ -416,6 +416,36 @@ _sig("lsdr_rate_est_run_async", C.c_int, [vp, vp, psz])
 _sig("lsdr_rate_est_wait", C.c_int, [vp, C.POINTER(RateEstimate)])
 
 
+HSYM_PACKED2, HSYM_U8, HSYM_SOFT = 0, 1, 2   # lsdr_fec_est's input formats
+
+
+class FecEstCfg(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("max_symbols", C.c_size_t), ("in_format", C.c_int), ("reserved", C.c_int * 5)]
+
+
+class FecEstScore(C.Structure):
+    _fields_ = [("errors", C.c_uint64), ("checks", C.c_uint64), ("sync", C.c_uint32), ("skip", C.c_uint32)]
+
+
+class FecEstimate(C.Structure):
+    """lsdr_fec_estimate: one stream's estimated code rate."""
+    _fields_ = [("fec", C.c_int32), ("locked", C.c_uint32), ("ambiguous", C.c_uint32), ("sync", C.c_uint32), ("skip", C.c_uint32),
+                ("pad", C.c_uint32), ("symbols", C.c_uint64), ("error_rate", C.c_float), ("runner_up", C.c_float), ("score", FecEstScore * 5)]
+
+    def as_dict(self):
+        return dict(fec=int(self.fec), locked=int(self.locked), ambiguous=int(self.ambiguous), sync=int(self.sync), skip=int(self.skip),
+                    symbols=int(self.symbols), error_rate=float(self.error_rate), runner_up=float(self.runner_up),
+                    score=[dict(errors=int(s.errors), checks=int(s.checks), sync=int(s.sync), skip=int(s.skip)) for s in self.score])
+
+
+_sig("lsdr_fec_est_create", C.c_int, [vp, C.POINTER(FecEstCfg), C.POINTER(vp)])
+_sig("lsdr_fec_est_destroy", None, [vp])
+_sig("lsdr_fec_est_tile", C.c_uint, [vp])
+_sig("lsdr_fec_est_run_async", C.c_int, [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+_sig("lsdr_fec_est_wait", C.c_int, [vp, C.POINTER(FecEstimate)])
+_sig("lsdr_fec_est_polys", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)])
+
+
 class ResampleBatchCfg(C.Structure):
     _fields_ = [("n_captures", C.c_int), ("max_samples", C.c_size_t), ("in_format", C.c_int), ("in_scale", C.c_float), ("ncoeffs", C.c_uint),
                 ("coeffs_host", vp), ("decim", C.c_uint), ("reserved", C.c_int * 6)]
@@ -1061,6 +1091,71 @@ def group_by_omega(estimates, rtol=1e-3, min_quality=RATE_MIN_QUALITY):
     return out, left
 
 
+class FecEstimator:
+    """lsdr_fec_est: the code rate of each of n_streams streams of hard QPSK symbols, estimated from the first max_symbols of them — the
+    fec the batch decoders want at construction.  The parity checks deconv[b] ^ deconv2[b] of deconvol_sync's --fastlock, swept over the
+    five rates, every symbol phase of the puncturing pattern and the four alignments (include/lsdr_hip.h)."""
+
+    def __init__(self, ctx, n_streams, max_symbols=16384, in_format=HSYM_PACKED2):
+        self.ctx, self.n, self.h = ctx, int(n_streams), None
+        cfg = FecEstCfg()
+        cfg.n_streams, cfg.max_symbols, cfg.in_format = self.n, int(max_symbols), int(in_format)
+        h = vp()
+        check(lib.lsdr_fec_est_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.max_symbols, self.in_format = int(max_symbols), int(in_format)
+        self._out = (FecEstimate * self.n)()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_fec_est_destroy(self.h)
+            self.h = None
+
+    @property
+    def tile(self):
+        """The symbols per workgroup tile of the score kernel."""
+        return int(lib.lsdr_fec_est_tile(self.h))
+
+    def run_async(self, ptrs, n, offsets=None):
+        """Queues the estimate: ptrs device pointers (None where n is 0), n symbols per stream, offsets the first symbol's position in the
+        stream at the pointer (None: zeros)."""
+        n = [int(v) for v in n]
+        off = [0] * self.n if offsets is None else [int(v) for v in offsets]
+        if len(n) != self.n or len(ptrs) != self.n or len(off) != self.n:
+            raise LsdrError(f"fec estimator: {len(ptrs)} pointers, {len(n)} lengths and {len(off)} offsets for {self.n} streams")
+        p = (vp * self.n)(*[q if isinstance(q, vp) else vp(q) for q in ptrs])
+        check(lib.lsdr_fec_est_run_async(self.h, p, (C.c_uint64 * self.n)(*off) if offsets is not None else None, (C.c_uint64 * self.n)(*n)))
+
+    def wait(self):
+        check(lib.lsdr_fec_est_wait(self.h, self._out))
+        return [r.as_dict() for r in self._out]
+
+    def estimate(self, ptrs, n, offsets=None):
+        """One run, synchronously: [dict(fec, locked, ambiguous, sync, skip, symbols, error_rate, runner_up, score [5 × dict(errors, checks,
+        sync, skip)])] per stream."""
+        self.run_async(ptrs, n, offsets)
+        return self.wait()
+
+
+def fec_polys(rate):
+    """(deconv, deconv2, punctperiod, punctweight) a rate is scored with: lsdr_fec_est_polys, what lsdr_deconv_create computes."""
+    d, d2, pw = (C.c_uint64 * 8)(), (C.c_uint64 * 8)(), C.c_int()
+    pp = lib.lsdr_fec_est_polys(int(rate), d, d2, C.byref(pw))
+    if pp <= 0:
+        raise LsdrError(f"lsdr_fec_est_polys: {lib.lsdr_last_error().decode()}")
+    return [int(v) for v in d[:pp]], [int(v) for v in d2[:pp]], pp, int(pw.value)
+
+
+def group_by_fec(estimates):
+    """The captures of a job sorted by code rate: ([(fec, [capture indices])], [indices left out]) from FecEstimator's records, in the
+    order 1/2, 2/3, 3/4, 5/6, 7/8 — the caller makes one CaptureBatch / HsBatch per group.  Left out, in their own list: records that
+    are not `locked` (nothing scored among them) and `ambiguous` ones."""
+    good = [i for i, e in enumerate(estimates) if e["locked"] and not e["ambiguous"] and e["fec"] >= 0]
+    left = [i for i in range(len(estimates)) if i not in set(good)]
+    groups = [(fec, [i for i in good if estimates[i]["fec"] == fec]) for fec in (FEC12, FEC23, FEC34, FEC56, FEC78)]
+    return [g for g in groups if g[1]], left
+
+
 class _TailBatch:
     """What the objects in front of the device-resident FEC tail share (CaptureBatch, HsBatch): a batch of self.n captures through
     run_async / wait, the TS download, and fetching TS and stage bytes.  A subclass sets _what, its name in error texts, and _c, the
@@ -1082,9 +1177,26 @@ class _TailBatch:
         if est:
             est[1].close()
             self._est = None
+        fest = getattr(self, "_fec_est", None)
+        if fest:
+            fest.close()
+            self._fec_est = None
         if self.h:
             self._fn("destroy")(self.h)
             self.h = None
+
+    def estimate_fec(self, results, max_symbols=16384):
+        """After a wait: every capture's code rate, estimated from the hard decisions the run left on the device (FecEstimator over the
+        first max_symbols of results[i]["symbols"]) — what `fec` this object should have been made with.  Reads what the front end wrote;
+        the decode is not touched."""
+        fmt, ptr = self._fec_symbols()
+        fest = getattr(self, "_fec_est", None)
+        if not fest or fest.max_symbols != int(max_symbols) or fest.in_format != fmt:
+            if fest:
+                fest.close()
+            self._fec_est = fest = FecEstimator(self.ctx, self.n, max_symbols, fmt)
+        n = [int(r["symbols"]) for r in results]
+        return fest.estimate([ptr(i) if n[i] else None for i in range(self.n)], n)
 
     def run_async(self, iq_ptrs, n_samples):
         check(self._run(self.h, self._ptrs(iq_ptrs), int(n_samples)))
@@ -1204,6 +1316,12 @@ class CaptureBatch(_TailBatch):
                 self.close()
                 raise
 
+    def _fec_symbols(self):
+        """estimate_fec's input: the soft symbols of a Viterbi object, the packed decisions otherwise."""
+        if self.viterbi:
+            return HSYM_SOFT, self.soft_ptr
+        return HSYM_PACKED2, lambda i: lib.lsdr_capture_batch_words_dev(self.h, int(i))
+
     def words(self, i, nsym):
         """The packed decisions of capture i after a run, unpacked (host)."""
         nw = (int(nsym) + 15) // 16
@@ -1282,6 +1400,9 @@ class HsBatch(_TailBatch):
         check(lib.lsdr_hs_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
         self.freq = float(freq)
         self._attach(h, lib.lsdr_hs_batch_run_async, lib.lsdr_hs_each_run_async)
+
+    def _fec_symbols(self):
+        return HSYM_U8, self.symbols_ptr
 
     def symbols_ptr(self, i):
         """Device pointer of capture i's hard symbols, one per byte (None for i out of range)."""

@@ -854,11 +854,7 @@ namespace {
 int log2u(unsigned long long x) { int n = -1; while (x) { ++n; x >>= 1; } return n; }
 int hpar(unsigned long long x) { return __builtin_parityll(x); }
 
-struct deconv_host {
-  unsigned conv[2], punct[2];
-  int pp, pw;
-  unsigned long long response[64], deconv[8], deconv2[8];
-};
+typedef lsdr_deconv_polys deconv_host;   // (lsdr_internal.h)
 unsigned long long dc_convolve(const deconv_host &d, unsigned long long s) {   // dvb.h:163-179
   const int sbits = log2u(s) + 1;
   unsigned long long iq = 0;
@@ -963,11 +959,9 @@ static gf_tables *rs_device_tables(lsdr_ctx *c) {   // one copy per context, cre
   return static_cast<gf_tables *>(c->rs_tables);
 }
 
-extern "C" {
-
-// ------------------------------------------------------------------ deconvol_sync
-int lsdr_deconv_create(lsdr_ctx *c, int rate, int fastlock, lsdr_deconv **out) {
-  LSDR_ARG(c && out);
+// deconvol_sync's constructor (dvb.h:122-293) for one rate: puncturing, the inverse polynomials and their alternates — the one place
+// that derives them, for lsdr_deconv_create and lsdr_fec_est (fec_est.hip).  deconv2[b] == deconv[b] where the reference has no alternate.
+int lsdr_deconv_polys_build(int rate, lsdr_deconv_polys *P) {
   unsigned pX, pY;
   switch (rate) {   // make_deconvol_sync_simple, dvb.h:480-513
     case LSDR_FEC12: pX = 0x1; pY = 0x1; break;
@@ -977,10 +971,8 @@ int lsdr_deconv_create(lsdr_ctx *c, int rate, int fastlock, lsdr_deconv **out) {
     case LSDR_FEC78: pX = 0x45; pY = 0x7a; break;
     default: pX = pY = 1;
   }
-  LSDR_HIP(hipSetDevice(c->device));
-  lsdr_deconv *d = new lsdr_deconv();
-  d->ctx = c;
-  deconv_host &H = d->H;
+  deconv_host &H = *P;
+  memset(&H, 0, sizeof(H));
   H.conv[0] = 0171; H.conv[1] = 0133;   // DVBS_G1, DVBS_G2 (dvb.h:84-85)
   H.punct[0] = pX; H.punct[1] = pY;
   H.pp = 0; H.pw = 0;
@@ -995,26 +987,10 @@ int lsdr_deconv_create(lsdr_ctx *c, int rate, int fastlock, lsdr_deconv **out) {
     dc_solve(H, 0, 0, (unsigned long long)(1 << b), &H.deconv[b]);
     for (int i = 0; i < 64; ++i)   // D·C = e_b check of the reference (dvb.h:274-283)
       if (hpar(dc_convolve(H, 1ull << i) & H.deconv[b]) != (b == i ? 1 : 0)) {
-        delete d;
         lsdr_set_error("deconvol_sync: failed to inverse convolutional coding");
         return LSDR_E_ARG;
       }
   }
-  // init_syncs, dvb.h:309-366: lut[re_pos][im_pos]; symbol bit1 ↔ first index, bit0 ↔ second (dvb.h:377)
-  for (int id = 0; id < 4; ++id)
-    for (int sym = 0; sym < 4; ++sym) {
-      const int re_pos = (sym & 2) ? 1 : 0, im_pos = sym & 1, re_neg = !re_pos;
-      int I = 0, Q = 0;
-      switch (id) {
-        case 0: I = re_pos ? 0 : 1; Q = im_pos ? 0 : 1; break;
-        case 1: I = im_pos ? 0 : 1; Q = re_neg ? 0 : 1; break;
-        case 2: I = re_pos ? 0 : 1; Q = im_pos ? 1 : 0; break;
-        case 3: I = im_pos ? 1 : 0; Q = re_neg ? 0 : 1; break;
-      }
-      d->luts[id][sym] = (unsigned char)((I << 1) | Q);
-    }
-  d->locked = 0; d->skip = 0;
-  d->fastlock = fastlock ? 1 : 0;
   for (int b = 0; b < H.pp; ++b) {   // alternate inverse polynomials of the reference (dvb.h:236-264)
     static const unsigned long long alt[][2] = {
         {0x3baULL, 0x38ccaULL},
@@ -1026,9 +1002,45 @@ int lsdr_deconv_create(lsdr_ctx *c, int rate, int fastlock, lsdr_deconv **out) {
         {0xfb112d5038dcULL, 0xfb112d5038271cULL}, {0xfbea3c7d68ULL, 0xfbeac7975462a8ULL},
         {0xfb112d50ULL, 0xfbea3c86793290ULL}, {0xfb112dabd2e0ULL, 0xfb112d50c3cd20ULL},
         {0xfb11d640ULL, 0xfbea3c8679c980ULL}};
-    d->deconv2[b] = H.deconv[b];
+    H.deconv2[b] = H.deconv[b];
     for (size_t i = 0; i < sizeof(alt) / sizeof(alt[0]); ++i)
-      if (H.deconv[b] == alt[i][0]) d->deconv2[b] = alt[i][1];
+      if (H.deconv[b] == alt[i][0]) H.deconv2[b] = alt[i][1];
+  }
+  return LSDR_OK;
+}
+
+// init_syncs, dvb.h:309-366: lut[re_pos][im_pos]; symbol bit1 ↔ first index, bit0 ↔ second (dvb.h:377)
+void lsdr_deconv_luts(unsigned char luts[4][4]) {
+  for (int id = 0; id < 4; ++id)
+    for (int sym = 0; sym < 4; ++sym) {
+      const int re_pos = (sym & 2) ? 1 : 0, im_pos = sym & 1, re_neg = !re_pos;
+      int I = 0, Q = 0;
+      switch (id) {
+        case 0: I = re_pos ? 0 : 1; Q = im_pos ? 0 : 1; break;
+        case 1: I = im_pos ? 0 : 1; Q = re_neg ? 0 : 1; break;
+        case 2: I = re_pos ? 0 : 1; Q = im_pos ? 1 : 0; break;
+        case 3: I = im_pos ? 1 : 0; Q = re_neg ? 0 : 1; break;
+      }
+      luts[id][sym] = (unsigned char)((I << 1) | Q);
+    }
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------ deconvol_sync
+int lsdr_deconv_create(lsdr_ctx *c, int rate, int fastlock, lsdr_deconv **out) {
+  LSDR_ARG(c && out);
+  LSDR_HIP(hipSetDevice(c->device));
+  lsdr_deconv *d = new lsdr_deconv();
+  d->ctx = c;
+  deconv_host &H = d->H;
+  const int prc = lsdr_deconv_polys_build(rate, &H);
+  if (prc) { delete d; return prc; }
+  lsdr_deconv_luts(d->luts);
+  d->locked = 0; d->skip = 0;
+  d->fastlock = fastlock ? 1 : 0;
+  for (int b = 0; b < H.pp; ++b) {
+    d->deconv2[b] = H.deconv2[b];
     if (fastlock && d->deconv2[b] == H.deconv[b]) {
       delete d;
       lsdr_set_error("deconvol_sync: Alt polynomial not provided");   // fail() of dvb.h:265

@@ -139,6 +139,18 @@ struct lsdr_tail_vit { unsigned long long bytes; unsigned alignment, pad; };   /
 int lsdr_tail_set_mpeg_sync(lsdr_tail *t, int fastlock, int resync_period);
 lsdr_tail_vit *lsdr_tail_vit_dev(lsdr_tail *t);
 
+// fec.hip: what deconvol_sync's constructor derives for one code rate (dvb.h:122-293, 480-513) — the puncturing patterns, punctperiod (pp),
+// punctweight (pw), the inverse polynomials deconv[0 … pp) and their alternates deconv2 (equal to deconv where the reference lists none).
+// Host only.  lsdr_deconv_create and lsdr_fec_est_create (fec_est.hip) both take their polynomials from here.
+struct lsdr_deconv_polys {
+  unsigned conv[2], punct[2];
+  int pp, pw;
+  unsigned long long response[64], deconv[8], deconv2[8];
+};
+int lsdr_deconv_polys_build(int rate, lsdr_deconv_polys *P);
+// … and init_syncs' four alignments (dvb.h:308-360): luts[alignment][symbol & 3] = the symbol's I/Q bits, I << 1 | Q
+void lsdr_deconv_luts(unsigned char luts[4][4]);
+
 // Host-side table builders (host_tables.cpp)
 namespace lsdr {
 void fir_shift_coeffs(unsigned ncoeffs, const float *coeffs, float freq, lsdr_cf32 *shifted);
