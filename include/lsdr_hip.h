@@ -1226,6 +1226,77 @@ int  lsdr_spectrum_batch_cnr(lsdr_spectrum_batch*, int i, float *cnr_out, size_t
 int  lsdr_spectrum_batch_rows_db(lsdr_spectrum_batch*, int i, float *rows_out, size_t cap_rows, size_t *n);
 const float *lsdr_spectrum_batch_rows_dev(const lsdr_spectrum_batch*, int i);
 
+/* ------------------------------------------------------------ TS batch: census and PID filter of many transport streams
+ * What a decoded TS is worth, and the part of it a user wants, without downloading and parsing all of it.  The reference drops every
+ * packet Reed-Solomon could not repair (derandomizer sets TEI and does not write it, dvb.h:1146-1156): a loss leaves no byte in the TS,
+ * only a jump of the MPEG continuity counter of the PID it hit.  This object reads B finished TS buffers in device memory — the batch
+ * decoders' *_ts_dev(i) or any uploaded TS, each with its own length — in shared launches and touches no decode kernel.
+ *
+ * THE DEFINITION (ISO 13818-1 §2.4.3).  All integers: every implementation agrees bit for bit, and a record is a pure function of the
+ * stream's bytes — the same alone, in any batch and at any tile size.  Packet k of a stream is the bytes b[0 … 187] at 188·k.
+ *   class    b[0] != 0x47: sync_errors, nothing else is read from the packet; else b[1] & 0x80: tei, nothing else is read (its PID cannot
+ *            be trusted); else the packet is VALID.
+ *   fields   of a valid packet: pid = (b[1]&0x1f)<<8 | b[2]; pusi = b[1]>>6 & 1; scrambled = (b[3]&0xc0) != 0; afc = b[3]>>4 & 3,
+ *            payload = afc&1, af = afc>>1; cc = b[3]&15; af_len = af ? b[4] : 0; disc = af && af_len > 0 && (b[5]&0x80);
+ *            pcr = af && af_len >= 7 && (b[5]&0x10); its value base·300 + ext, base = b[6]<<25 | b[7]<<17 | b[8]<<9 | b[9]<<1 | b[10]>>7,
+ *            ext = (b[10]&1)<<8 | b[11].
+ *   null     pid 0x1fff counts in null_packets and in its own record (packets, pusi, scrambled, pcr_count, first, last); it is never
+ *            continuity-checked.
+ *   continuity  per PID other than 0x1fff, over that PID's valid packets in stream order; the first is not judged.  For every later
+ *            packet cur with predecessor prev: cur.disc → discontinuities++; otherwise expected = (prev.cc + cur.payload) & 15;
+ *            cur.cc == expected is fine; else cur.payload && cur.cc == prev.cc → cc_repeats++ (the standard's legal duplicate, not
+ *            judged further); else cc_errors++ and cc_missing += (cur.cc − expected) & 15.  The rule looks at the pair only.
+ *   PCR      pcr_pid is the PID of the first valid packet in stream order with pcr set (−1: none); pcr_count, pcr_first, pcr_last
+ *            (27 MHz ticks), pcr_first_packet and pcr_last_packet (indices among ALL packets of the stream) refer to that PID only.
+ * The summary's four continuity totals run over ALL PIDs of the stream, listed or not.  The table of lsdr_ts_batch_pids holds the
+ * min(pids_seen, max_pids) LOWEST PIDs in ascending order.
+ * THE FILTER (a run with a rule).  A packet is kept iff `drop` does not drop it (sync-error and TEI packets by their class, null packets
+ * by their PID) and it is a sync-error or TEI packet, or keep_pids is NULL, or its PID's bit is set; sync-error and TEI packets have no
+ * PID, keep_pids does not apply to them.  The kept packets stand in stream order at lsdr_ts_batch_out_dev(i), kept·188 bytes; with
+ * want_index, lsdr_ts_batch_index_dev(i) holds each one's index in the input.  `kept` is 0 after a run without a rule.
+ * QUEUEING.  run_async queues everything on the context's stream and returns; one run in flight per object; wait is one synchronisation
+ * and the read of pinned records.  download_async (after the wait of a run with a rule) copies kept·188 bytes per stream on a stream of
+ * its own and may still be pending when the next run_async is queued: the kernels that write the output wait for it.
+ * LIMITS: 188-byte packets only.  No PSI parsing: PAT and PMT are the user's to read from the filtered PID 0.  Continuity says how many
+ * packets a PID lost modulo 16: cc_missing is a lower bound on the loss.  The per-PID counters are 32 bits wide.
+ * LSDR_E_ARG, with a message naming ts_batch, the object (if any) left usable: n_streams < 1 (or above 65535), max_pids > 8192, nonzero
+ * reserved, n_packets[i] > max_packets, a NULL or not 4-byte aligned pointer with packets, unknown drop bits, run_async with a run in
+ * flight, wait with none, a download before the wait of a run with a rule or into cap_bytes smaller than some stream's kept bytes, i out
+ * of range.  LSDR_E_UNSUPPORTED: max_packets ≥ 2^32. */
+enum { LSDR_TS_DROP_NULL = 1, LSDR_TS_DROP_TEI = 2, LSDR_TS_DROP_SYNC = 4 };
+typedef struct lsdr_ts_batch lsdr_ts_batch;
+typedef struct { int n_streams; size_t max_packets; unsigned max_pids; /* 0: 64; at most 8192 */ int reserved[8]; } lsdr_ts_batch_cfg;
+typedef struct {
+  const uint8_t *keep_pids;  /* HOST; NULL: all PIDs; else n_streams × 1024 bytes, bit (pid & 7) of byte pid >> 3 of stream i's 1024 */
+  unsigned drop;             /* LSDR_TS_DROP_NULL | _TEI | _SYNC */
+  int want_index;
+  int reserved[4];           /* 0 */
+} lsdr_ts_rule;
+typedef struct {
+  uint64_t packets, sync_errors, tei, null_packets, valid, cc_errors, cc_repeats, cc_missing, discontinuities, kept,
+           pcr_first, pcr_last, pcr_first_packet, pcr_last_packet;
+  uint32_t pids_seen, pids_listed;
+  int32_t pcr_pid;
+  uint32_t pcr_count;
+} lsdr_ts_summary;           /* 128 bytes */
+typedef struct {
+  uint32_t pid, packets, pusi, scrambled, cc_errors, cc_repeats, cc_missing, discontinuities, pcr_count, pad;
+  uint64_t first_packet, last_packet;
+} lsdr_ts_pid;               /* 56 bytes */
+int  lsdr_ts_batch_create(lsdr_ctx*, const lsdr_ts_batch_cfg*, lsdr_ts_batch**);
+void lsdr_ts_batch_destroy(lsdr_ts_batch*);
+/* ts_dev: HOST array of DEVICE pointers, 4-byte aligned (may be NULL where n_packets is 0); n_packets: HOST; rule NULL: census only */
+int  lsdr_ts_batch_run_async(lsdr_ts_batch*, const uint8_t *const *ts_dev, const uint64_t *n_packets, const lsdr_ts_rule *rule);
+int  lsdr_ts_batch_wait(lsdr_ts_batch*, lsdr_ts_summary *out /* [n_streams], may be NULL */);
+/* after wait: stream i's table, *n = pids_listed entries where cap allows (LSDR_E_ARG, nothing written, where it does not) */
+int  lsdr_ts_batch_pids(lsdr_ts_batch*, int i, lsdr_ts_pid *out, unsigned cap, unsigned *n);
+const uint8_t *lsdr_ts_batch_out_dev(const lsdr_ts_batch*, int i);     /* NULL before the first run with a rule, or i out of range */
+const uint32_t *lsdr_ts_batch_index_dev(const lsdr_ts_batch*, int i);  /* NULL unless the last run's rule had want_index */
+int  lsdr_ts_batch_download_async(lsdr_ts_batch*, uint8_t *const *host /* [n_streams] HOST pointers */, size_t cap_bytes);
+int  lsdr_ts_batch_download_wait(lsdr_ts_batch*);
+/* packets per workgroup tile: the lengths at which the kernels change their path are multiples of it */
+unsigned lsdr_ts_batch_tile(const lsdr_ts_batch*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -485,6 +485,48 @@ _sig("lsdr_spectrum_batch_cnr", C.c_int, [vp, C.c_int, vp, c_sz, psz])
 _sig("lsdr_spectrum_batch_rows_db", C.c_int, [vp, C.c_int, vp, c_sz, psz])
 _sig("lsdr_spectrum_batch_rows_dev", vp, [vp, C.c_int])
 
+
+TS_DROP_NULL, TS_DROP_TEI, TS_DROP_SYNC = 1, 2, 4   # lsdr_ts_rule.drop
+
+
+class TsBatchCfg(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("max_packets", C.c_size_t), ("max_pids", C.c_uint), ("reserved", C.c_int * 8)]
+
+
+class TsRule(C.Structure):
+    _fields_ = [("keep_pids", vp), ("drop", C.c_uint), ("want_index", C.c_int), ("reserved", C.c_int * 4)]
+
+
+class TsSummary(C.Structure):
+    """lsdr_ts_summary: one transport stream's census."""
+    _fields_ = [(k, C.c_uint64) for k in ("packets", "sync_errors", "tei", "null_packets", "valid", "cc_errors", "cc_repeats", "cc_missing",
+                                          "discontinuities", "kept", "pcr_first", "pcr_last", "pcr_first_packet", "pcr_last_packet")] + \
+               [("pids_seen", C.c_uint32), ("pids_listed", C.c_uint32), ("pcr_pid", C.c_int32), ("pcr_count", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class TsPid(C.Structure):
+    """lsdr_ts_pid: one PID of a stream's table."""
+    _fields_ = [(k, C.c_uint32) for k in ("pid", "packets", "pusi", "scrambled", "cc_errors", "cc_repeats", "cc_missing", "discontinuities",
+                                          "pcr_count", "pad")] + [("first_packet", C.c_uint64), ("last_packet", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+_sig("lsdr_ts_batch_create", C.c_int, [vp, C.POINTER(TsBatchCfg), C.POINTER(vp)])
+_sig("lsdr_ts_batch_destroy", None, [vp])
+_sig("lsdr_ts_batch_run_async", C.c_int, [vp, vp, C.POINTER(C.c_uint64), C.POINTER(TsRule)])
+_sig("lsdr_ts_batch_wait", C.c_int, [vp, C.POINTER(TsSummary)])
+_sig("lsdr_ts_batch_pids", C.c_int, [vp, C.c_int, C.POINTER(TsPid), C.c_uint, C.POINTER(C.c_uint)])
+_sig("lsdr_ts_batch_out_dev", vp, [vp, C.c_int])
+_sig("lsdr_ts_batch_index_dev", vp, [vp, C.c_int])
+_sig("lsdr_ts_batch_download_async", C.c_int, [vp, vp, c_sz])
+_sig("lsdr_ts_batch_download_wait", C.c_int, [vp])
+_sig("lsdr_ts_batch_tile", C.c_uint, [vp])
+
 #: decode_estimated's default threshold on `quality`: the geometric mean of what Gaussian noise alone reaches (3.1) and the weakest of the
 #: test captures (347), rounded (DESIGN.md §4.8)
 TUNE_MIN_QUALITY = 30.0
@@ -1156,6 +1198,130 @@ def group_by_fec(estimates):
     return [g for g in groups if g[1]], left
 
 
+class TsBatch:
+    """lsdr_ts_batch: the census (packet classes, per-PID continuity counters, PCR) and the PID filter of n_streams transport streams in
+    device memory, each with its own length, in shared launches (include/lsdr_hip.h).  The table of a stream holds its max_pids lowest
+    PIDs."""
+
+    def __init__(self, ctx, n_streams, max_packets, max_pids=64):
+        self.ctx, self.n, self.h = ctx, int(n_streams), None
+        cfg = TsBatchCfg()
+        cfg.n_streams, cfg.max_packets, cfg.max_pids = self.n, int(max_packets), int(max_pids)
+        h = vp()
+        check(lib.lsdr_ts_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.max_packets, self.max_pids = int(max_packets), int(max_pids) or 64
+        self._sum = (TsSummary * max(self.n, 1))()
+        self._tab = (TsPid * self.max_pids)()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_ts_batch_destroy(self.h)
+            self.h = None
+
+    @property
+    def tile(self):
+        """The packets per workgroup tile."""
+        return int(lib.lsdr_ts_batch_tile(self.h))
+
+    def keep_bitmap(self, keep_pids):
+        """lsdr_ts_rule.keep_pids from a list of PIDs (for every stream) or a list of such lists, one per stream: uint8 [n][1024]."""
+        per = list(keep_pids)
+        if not per or np.isscalar(per[0]):
+            per = [per] * self.n
+        if len(per) != self.n:
+            raise LsdrError(f"ts batch: {len(per)} PID lists for {self.n} streams")
+        bm = np.zeros((self.n, 1024), np.uint8)
+        for i, pids in enumerate(per):
+            for p in pids:
+                if not 0 <= int(p) < 8192:
+                    raise LsdrError(f"ts batch: PID {p} is outside 0 … 8191")
+                bm[i, int(p) >> 3] |= 1 << (int(p) & 7)
+        return bm
+
+    def run_async(self, ptrs, n_packets, rule=None):
+        """Queues one run: ptrs device pointers (None where there are no packets), n_packets per stream, rule a TsRule or None (census)."""
+        n = [int(v) for v in n_packets]
+        if len(n) != self.n or len(ptrs) != self.n:
+            raise LsdrError(f"ts batch: {len(ptrs)} pointers and {len(n)} lengths for {self.n} streams")
+        p = (vp * self.n)(*[q if isinstance(q, vp) else vp(q) for q in ptrs])
+        check(lib.lsdr_ts_batch_run_async(self.h, p, (C.c_uint64 * self.n)(*n), C.byref(rule) if rule is not None else None))
+
+    def pids(self, i):
+        """Stream i's table after a wait: [dict(pid, packets, pusi, scrambled, cc_errors, cc_repeats, cc_missing, discontinuities,
+        pcr_count, first_packet, last_packet)], ascending in pid."""
+        n = C.c_uint()
+        check(lib.lsdr_ts_batch_pids(self.h, int(i), self._tab, self.max_pids, C.byref(n)))
+        return [self._tab[k].as_dict() for k in range(n.value)]
+
+    def wait(self):
+        """[summary dict with "pids": the stream's table] per stream."""
+        check(lib.lsdr_ts_batch_wait(self.h, self._sum))
+        out = [s.as_dict() for s in self._sum[:self.n]]
+        for i, s in enumerate(out):
+            s["pids"] = self.pids(i)
+        return out
+
+    def census(self, ptrs, n_packets):
+        """One run without a rule, synchronously."""
+        self.run_async(ptrs, n_packets)
+        return self.wait()
+
+    def rule(self, keep_pids=None, drop_null=True, drop_tei=True, drop_sync=True, index=False):
+        """(TsRule, the array its keep_pids points to: keep it alive until run_async has returned)."""
+        r = TsRule()
+        bm = None if keep_pids is None else self.keep_bitmap(keep_pids)
+        r.keep_pids = None if bm is None else bm.ctypes.data
+        r.drop = (TS_DROP_NULL if drop_null else 0) | (TS_DROP_TEI if drop_tei else 0) | (TS_DROP_SYNC if drop_sync else 0)
+        r.want_index = 1 if index else 0
+        return r, bm
+
+    def out_ptr(self, i):
+        return lib.lsdr_ts_batch_out_dev(self.h, int(i))
+
+    def index_ptr(self, i):
+        return lib.lsdr_ts_batch_index_dev(self.h, int(i))
+
+    def download_async(self, host_arrays, cap_bytes=None):
+        """Queues the copy of every stream's kept packets into host_arrays[i] (uint8 numpy arrays of cap_bytes, default the smallest)."""
+        cap = min(a.nbytes for a in host_arrays) if cap_bytes is None else int(cap_bytes)
+        check(lib.lsdr_ts_batch_download_async(self.h, (vp * self.n)(*[a.ctypes.data for a in host_arrays]), cap))
+
+    def download_wait(self):
+        check(lib.lsdr_ts_batch_download_wait(self.h))
+
+    def filter(self, ptrs, n_packets, keep_pids=None, drop_null=True, drop_tei=True, drop_sync=True, index=False):
+        """One run with a rule, synchronously: (summaries, [the kept packets' bytes per stream], [uint32 arrays of their indices in the
+        input] or None).  keep_pids: None (every PID), a list of PIDs, or a list of such lists, one per stream."""
+        r, bm = self.rule(keep_pids, drop_null, drop_tei, drop_sync, index)
+        self.run_async(ptrs, n_packets, r)
+        res = self.wait()
+        cap = max([s["kept"] for s in res] + [1]) * 188
+        bufs = [np.empty(cap, np.uint8) for _ in range(self.n)]
+        self.download_async(bufs, cap)
+        idx = None
+        if index:
+            idx = [np.empty(s["kept"], np.uint32) for s in res]
+            for i, a in enumerate(idx):
+                if len(a):
+                    check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(a), self.index_ptr(i), a.nbytes))
+            self.ctx.sync()
+        self.download_wait()
+        return res, [b[:s["kept"] * 188].tobytes() for b, s in zip(bufs, res)], idx
+
+
+def ts_bitrate(summary):
+    """The stream's bit rate from its PCRs: the bits between the first and the last packet that carry one, over the time between the two
+    values (27 MHz ticks, the 33-bit base wraps).  None with fewer than two PCRs or no difference."""
+    if summary["pcr_count"] < 2:
+        return None
+    ticks = (summary["pcr_last"] - summary["pcr_first"]) % ((1 << 33) * 300)
+    packets = summary["pcr_last_packet"] - summary["pcr_first_packet"]
+    if not ticks or not packets:
+        return None
+    return packets * 188 * 8 * 27e6 / ticks
+
+
 class _TailBatch:
     """What the objects in front of the device-resident FEC tail share (CaptureBatch, HsBatch): a batch of self.n captures through
     run_async / wait, the TS download, and fetching TS and stage bytes.  A subclass sets _what, its name in error texts, and _c, the
@@ -1181,9 +1347,35 @@ class _TailBatch:
         if fest:
             fest.close()
             self._fec_est = None
+        tsb = getattr(self, "_ts_batch", None)
+        if tsb:
+            tsb.close()
+            self._ts_batch = None
         if self.h:
             self._fn("destroy")(self.h)
             self.h = None
+
+    def _ts_object(self, results):
+        """(the cached TsBatch, sized for the longest TS so far; every capture's TS pointer; its packets) after a wait."""
+        n = [int(r["ts_packets"]) for r in results]
+        tsb = getattr(self, "_ts_batch", None)
+        if not tsb or tsb.max_packets < max(n + [1]):
+            if tsb:
+                tsb.close()
+            self._ts_batch = tsb = TsBatch(self.ctx, self.n, max(n + [1]))
+        return tsb, [self._fn("ts_dev")(self.h, i) if n[i] else None for i in range(self.n)], n
+
+    def ts_census(self, results):
+        """After a wait: the census of every capture's TS where the run left it on the device (TsBatch.census over ts_dev(i) and
+        results[i]["ts_packets"]).  The decode is not touched."""
+        tsb, ptrs, n = self._ts_object(results)
+        return tsb.census(ptrs, n)
+
+    def ts_filter(self, results, **rule):
+        """After a wait: TsBatch.filter over every capture's TS on the device — (summaries, [kept bytes], [indices] or None); rule:
+        keep_pids, drop_null, drop_tei, drop_sync, index."""
+        tsb, ptrs, n = self._ts_object(results)
+        return tsb.filter(ptrs, n, **rule)
 
     def estimate_fec(self, results, max_symbols=16384):
         """After a wait: every capture's code rate, estimated from the hard decisions the run left on the device (FecEstimator over the
