@@ -948,8 +948,8 @@ int lsdr_hs_each_run_async(lsdr_hs_batch *b, const lsdr_cu8 *const *iq_dev, cons
  * the read of B records.  One run in flight per object.
  * iq_dev: HOST array of B DEVICE pointers, each aligned to its item size (2, 2, 4, 4, 8 bytes for cu8, cs8, cu16, cs16, cf32; a 16-byte
  * aligned capture is read by 16-byte loads), NULL only where n_samples[i] is 0.  Nothing behind block M − 1 of a capture is read.
- * LSDR_E_ARG, with a message, the object (if any) left usable: n_captures < 1, in_format outside the five LSDR_IN_*, in_scale negative or
- * not finite, blocks > 64, nonzero reserved; a misaligned pointer, samples without a pointer, run_async with a run in flight, wait with none. */
+ * LSDR_E_ARG, with a message, the object (if any) left usable: n_captures < 1 (or above 65535), in_format outside the five LSDR_IN_*, in_scale
+ * negative or not finite, blocks > 64, nonzero reserved; a misaligned pointer, samples without a pointer, run_async with a run in flight, wait with none. */
 typedef struct lsdr_tune_est lsdr_tune_est;
 typedef struct {
   int n_captures;      /* B */

@@ -1034,81 +1034,72 @@ class RxBatch:
         return st
 
 
-class TuneEstimator:
-    """lsdr_tune_est: the carrier offset of each of n_captures captures, estimated from the raw samples (QPSK: the spectral line of the
-    fourth power, over the first `blocks` blocks of 4096 samples) — the number the batch decoders' per-capture tune wants."""
+class _BlockEstimator:
+    """What TuneEstimator and RateEstimator share: one object per batch of n captures, (pointers, lengths) in, one record per capture out.
+    A subclass names its entry points (lsdr_<_name>_create / _destroy / _run_async / _wait), its record type and its word in the error text."""
+    _name = _word = _record = None
 
-    def __init__(self, ctx, n_captures, in_format=IN_CU8, in_scale=0.0, blocks=8):
+    def _create(self, ctx, cfg, n_captures, in_format, in_scale, blocks):
         self.ctx, self.n, self.h = ctx, int(n_captures), None
-        cfg = TuneEstCfg()
         cfg.n_captures, cfg.in_format, cfg.in_scale, cfg.blocks = self.n, int(in_format), float(in_scale), int(blocks)
         h = vp()
-        check(lib.lsdr_tune_est_create(ctx.h, C.byref(cfg), C.byref(h)))
+        check(self._fn("create")(ctx.h, C.byref(cfg), C.byref(h)))
         self.h = h
-        self._out = (TuneEstimate * self.n)()
+        self._out = (self._record * self.n)()
+
+    def _fn(self, what):
+        return getattr(lib, f"lsdr_{self._name}_{what}")
 
     def close(self):
         if self.h:
-            lib.lsdr_tune_est_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def _args(self, iq_ptrs, n_samples):
         n = [int(v) for v in n_samples]
         if len(n) != self.n or len(iq_ptrs) != self.n:
-            raise LsdrError(f"tune estimator: {len(iq_ptrs)} pointers and {len(n)} lengths for {self.n} captures")
+            raise LsdrError(f"{self._word} estimator: {len(iq_ptrs)} pointers and {len(n)} lengths for {self.n} captures")
         return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs]), (c_sz * self.n)(*n)
 
     def run_async(self, iq_ptrs, n_samples):
         """Queues the estimate of every capture's first n_samples[i] items; a pointer may be None where the length is 0."""
-        check(lib.lsdr_tune_est_run_async(self.h, *self._args(iq_ptrs, n_samples)))
+        check(self._fn("run_async")(self.h, *self._args(iq_ptrs, n_samples)))
 
     def wait(self):
-        check(lib.lsdr_tune_est_wait(self.h, self._out))
+        check(self._fn("wait")(self.h, self._out))
         return [r.as_dict() for r in self._out]
+
+    def estimate(self, iq_ptrs, n_samples):
+        self.run_async(iq_ptrs, n_samples)
+        return self.wait()
+
+
+class TuneEstimator(_BlockEstimator):
+    """lsdr_tune_est: the carrier offset of each of n_captures captures, estimated from the raw samples (QPSK: the spectral line of the
+    fourth power, over the first `blocks` blocks of 4096 samples) — the number the batch decoders' per-capture tune wants."""
+    _name, _word, _record = "tune_est", "tune", TuneEstimate
+
+    def __init__(self, ctx, n_captures, in_format=IN_CU8, in_scale=0.0, blocks=8):
+        self._create(ctx, TuneEstCfg(), n_captures, in_format, in_scale, blocks)
 
     def estimate(self, iq_ptrs, n_samples):
         """One run, synchronously: [dict(tune, quality, bin, blocks, power [l, c, r], mean_power)] per capture."""
-        self.run_async(iq_ptrs, n_samples)
-        return self.wait()
+        return super().estimate(iq_ptrs, n_samples)
 
 
-class RateEstimator:
+class RateEstimator(_BlockEstimator):
     """lsdr_rate_est: the samples per symbol of each of n_captures captures, estimated from the raw samples (RRC-shaped PSK: the spectral
     line of the squared magnitude, over the first `blocks` blocks of 4096 samples) — the omega the batch objects want at construction."""
+    _name, _word, _record = "rate_est", "rate", RateEstimate
 
     def __init__(self, ctx, n_captures, in_format=IN_CU8, in_scale=0.0, blocks=64, omega_min=0.0, omega_max=0.0):
-        self.ctx, self.n, self.h = ctx, int(n_captures), None
         cfg = RateEstCfg()
-        cfg.n_captures, cfg.in_format, cfg.in_scale, cfg.blocks = self.n, int(in_format), float(in_scale), int(blocks)
         cfg.omega_min, cfg.omega_max = float(omega_min), float(omega_max)
-        h = vp()
-        check(lib.lsdr_rate_est_create(ctx.h, C.byref(cfg), C.byref(h)))
-        self.h = h
-        self._out = (RateEstimate * self.n)()
-
-    def close(self):
-        if self.h:
-            lib.lsdr_rate_est_destroy(self.h)
-            self.h = None
-
-    def _args(self, iq_ptrs, n_samples):
-        n = [int(v) for v in n_samples]
-        if len(n) != self.n or len(iq_ptrs) != self.n:
-            raise LsdrError(f"rate estimator: {len(iq_ptrs)} pointers and {len(n)} lengths for {self.n} captures")
-        return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in iq_ptrs]), (c_sz * self.n)(*n)
-
-    def run_async(self, iq_ptrs, n_samples):
-        """Queues the estimate of every capture's first n_samples[i] items; a pointer may be None where the length is 0."""
-        check(lib.lsdr_rate_est_run_async(self.h, *self._args(iq_ptrs, n_samples)))
-
-    def wait(self):
-        check(lib.lsdr_rate_est_wait(self.h, self._out))
-        return [r.as_dict() for r in self._out]
+        self._create(ctx, cfg, n_captures, in_format, in_scale, blocks)
 
     def estimate(self, iq_ptrs, n_samples):
         """One run, synchronously: [dict(omega, other, line, quality, corr, bin, blocks, ambiguous, power [l, c, r], floor)] per capture."""
-        self.run_async(iq_ptrs, n_samples)
-        return self.wait()
+        return super().estimate(iq_ptrs, n_samples)
 
 
 def group_by_omega(estimates, rtol=1e-3, min_quality=RATE_MIN_QUALITY):

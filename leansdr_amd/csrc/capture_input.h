@@ -8,7 +8,8 @@
 //   in_run, lsdr_in_free                                   what the objects above the formats repeat: records, event, flag; destroy
 //
 // The conversion is rxb_device.h's (rxb_in<K>) for the kernels outside the receiver; the receiver's own loads stay where bench.py measures
-// them.  rxb_host.h ties the two enumerations together.
+// them.  rxb_host.h ties the two enumerations together.  block_spectrum.h stands on this header: what lsdr_tune_est and lsdr_rate_est share
+// above the formats (blocks of 4096 samples, their transform, the reductions, the host's frame of a run).
 #ifndef LSDR_CAPTURE_INPUT_H
 #define LSDR_CAPTURE_INPUT_H
 #include <cmath>

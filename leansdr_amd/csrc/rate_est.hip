@@ -7,10 +7,11 @@
 // per block s = mean |z|², p[n] = |z[n]|²/s − 1 (an all-zero block contributes zeros), X = FFT_N(p) with a rectangular window;
 // P[k] = Σ_blocks |X[k]|² in block order; c₁ = Σ_blocks Σ_{n ≥ 1} z[n]·conj(z[n − 1]) / s.  The first arg-max of P over [k_lo, N/2] with its
 // two neighbours above the floor gives the line; the lag-one correlation R = |c₁| / (M₁·(N − 1)) chooses between omega = 1/line and its
-// alias 1/(1 − line) (rate_est_device.h: re_peak_record).
+// alias 1/(1 − line) (rate_est_device.h: re_peak_record).  The staging, the workgroup sums, the transform, the first maximum and the host's
+// frame are block_spectrum.h's, shared with tune_est.hip; here are the three sums, the half row, the blocks' stats and the record.
 //
 //   k_re_block<K>   blockIdx.y = capture, blockIdx.x = block, one workgroup of 256: 16-byte loads (item-wise where the capture's pointer is
-//                   only item-aligned: the same values), the converted block in LDS (32 KB), Σ|z|² and the lag-one sum, p in place, tune_est's
+//                   only item-aligned: the same values), the converted block in LDS (32 KB), Σ|z|² and the lag-one sum, p in place, the
 //                   six radix-4 stages, |X|² of bins 0 … N/2 as one row of scratch, the block's (c₁/s, s) beside it
 //   k_re_peak       one workgroup per capture: the rows and the blocks' c₁ summed in block order, first maximum, floor; thread 0 writes
 //                   the record
@@ -20,14 +21,12 @@
 // bits alone, in any batch, in any place of it, and for every format that converts to the same floats.  Both kernels leave by the capture's
 // own block count: nothing is read behind block M − 1 of a capture, and nothing at all of one with M = 0.
 #include <cmath>
-#include "capture_input.h"
 #include "rate_est_device.h"
 
 namespace {
 
-struct re_cap { const unsigned char *in; unsigned blocks, pad; };
 struct re_args {
-  const re_cap *caps;
+  const bs_cap *caps;
   const float2 *tw;                    // [4096] exp(−j2π·i/4096)
   float *rows;                         // [captures][row_cap][kReRow] |X|² of every block, bins 0 … N/2
   float4 *stats;                       // [captures][row_cap] (re c₁/s, im c₁/s, s, 1) of every block; all zeros for a block with s = 0
@@ -39,42 +38,14 @@ struct re_args {
 };
 static_assert(sizeof(re_record) == sizeof(lsdr_rate_estimate) && sizeof(re_record) == 48, "lsdr_rate_estimate is re_record");
 
-// Σ over the workgroup of 256 of three values at once, the same in every thread: lanes by xor-shuffles, the four wavefronts in order
-__device__ __forceinline__ void re_sum256x3(float (&v)[3], float (*red)[4]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v[q] += __shfl_xor(v[q], d, 64);
-    if ((threadIdx.x & 63u) == 0) red[q][threadIdx.x >> 6] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 3; ++q) v[q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
-}
-
 template <int K>
 __global__ __launch_bounds__(256) void k_re_block(re_args A) {
-  const re_cap cap = A.caps[blockIdx.y];
+  const bs_cap cap = A.caps[blockIdx.y];
   if (blockIdx.x >= cap.blocks) return;
   __shared__ float2 x[kReN];
   __shared__ float red[3][4];
-  constexpr unsigned kB = in_item<K>::kBytes, kPer = 16u / kB;
   const unsigned t = threadIdx.x;
-  const unsigned char *src = cap.in + (size_t)blockIdx.x * kReN * kB;
-  // one 16-byte piece per thread and pass; the alignment is decided once, in front of the loop, and the loop stays rolled (tune_est.hip)
-  auto stage = [&](auto wide) {
-#pragma unroll 1
-    for (unsigned l = 0; l < kReN / (256u * kPer); ++l) {
-      const unsigned s0 = (l * 256u + t) * kPer;
-      float2 z[kPer];
-      in_piece<K>(src, s0, wide(), A.in_scale, A.in_flip, z);
-#pragma unroll
-      for (unsigned q = 0; q < kPer; ++q) x[s0 + q] = z[q];
-    }
-  };
-  if (((size_t)src & 15u) == 0) stage(std::true_type());     // (a block is a multiple of 16 bytes: the capture's own alignment decides)
-  else stage(std::false_type());
-  __syncthreads();
+  bs_stage<K>(cap.in, blockIdx.x, A.in_scale, A.in_flip, x);
   // Σ|z|² and Σ_{n ≥ 1} z[n]·conj(z[n − 1]): thread t takes n = t, t + 256, …
   float v[3] = {0.f, 0.f, 0.f};
   for (unsigned i = 0; i < kReN / 256u; ++i) {
@@ -87,24 +58,20 @@ __global__ __launch_bounds__(256) void k_re_block(re_args A) {
       v[2] += z.y * y.x - z.x * y.y;
     }
   }
-  re_sum256x3(v, red);                                       // (its barrier is behind every read of a neighbour's sample)
+  bs_sum256(v, red);                                         // (its barrier is behind every read of a neighbour's sample)
   const float s = v[0] * (1.0f / (float)kReN);
   const float inv = s > 0.f ? 1.0f / s : 0.f;
   for (unsigned i = 0; i < kReN / 256u; ++i) {
     const float2 z = x[t + 256u * i];
     x[t + 256u * i] = make_float2(s > 0.f ? (z.x * z.x + z.y * z.y) * inv - 1.0f : 0.f, 0.f);
   }
-  for (unsigned st = 0; st < kTeLog4; ++st) {
-    __syncthreads();
-    te_fft_stage(x, A.tw, st, t);
-  }
-  __syncthreads();
+  bs_fft(x, A.tw);
   const size_t slot = (size_t)blockIdx.y * A.row_cap + blockIdx.x;
   float *row = A.rows + slot * kReRow;
   for (unsigned i = 0; i <= kReHalf / 256u; ++i) {
     const unsigned k = t + 256u * i;
     if (k <= kReHalf) {
-      const float2 X = x[te_digit_reverse(k)];
+      const float2 X = x[bs_digit_reverse(k)];
       row[k] = X.x * X.x + X.y * X.y;
     }
   }
@@ -112,7 +79,7 @@ __global__ __launch_bounds__(256) void k_re_block(re_args A) {
 }
 
 __global__ __launch_bounds__(256) void k_re_peak(re_args A) {
-  const re_cap cap = A.caps[blockIdx.x];
+  const bs_cap cap = A.caps[blockIdx.x];
   const unsigned t = threadIdx.x;
   if (cap.blocks == 0) {
     if (t == 0) A.rec[blockIdx.x] = re_record{};             // no whole block: all zeros
@@ -120,8 +87,7 @@ __global__ __launch_bounds__(256) void k_re_peak(re_args A) {
   }
   __shared__ float P[kReHalf + 1u];
   __shared__ float4 st[kReMaxBlocks];
-  __shared__ float red[4], bestv[4];
-  __shared__ unsigned bestk[4];
+  __shared__ bs_peak_lds sh;
   const float *rows = A.rows + (size_t)blockIdx.x * A.row_cap * kReRow;
   if (t < cap.blocks) st[t] = A.stats[(size_t)blockIdx.x * A.row_cap + t];
   float sum = 0.f, best = -1.f;
@@ -137,21 +103,9 @@ __global__ __launch_bounds__(256) void k_re_peak(re_args A) {
       if (p > best) { best = p; bk = k; }                    // ascending k: the first maximum of this thread's bins
     }
   }
-  // the first maximum of all: the larger power, the smaller bin among equals (a thread without a searched bin holds −1)
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const float ov = __shfl_xor(best, d, 64);
-    const unsigned ok = (unsigned)__shfl_xor((int)bk, d, 64);
-    if (ov > best || (ov == best && ok < bk)) { best = ov; bk = ok; }
-    sum += __shfl_xor(sum, d, 64);
-  }
-  if ((t & 63u) == 0) { bestv[t >> 6] = best; bestk[t >> 6] = bk; red[t >> 6] = sum; }
-  __syncthreads();                                           // (publishes P and st as well)
+  bs_first_max(best, bk, sum, sh);                           // (a thread without a searched bin holds −1; its barrier publishes P and st as well)
   if (t == 0) {
-    for (unsigned w = 1; w < 4; ++w)
-      if (bestv[w] > best || (bestv[w] == best && bestk[w] < bk)) { best = bestv[w]; bk = bestk[w]; }
-    const float total = ((red[0] + red[1]) + red[2]) + red[3];
-    const float floor_ = total / (float)(kReHalf - A.k_lo + 1u);
+    const float floor_ = sum / (float)(kReHalf - A.k_lo + 1u);
     double cre = 0.0, cim = 0.0;                             // (the blocks' c₁ in block order, in double like the rest of the record)
     unsigned m1 = 0;
     for (unsigned b = 0; b < cap.blocks; ++b) { cre += (double)st[b].x; cim += (double)st[b].y; m1 += st[b].w != 0.f ? 1u : 0u; }
@@ -166,12 +120,9 @@ __global__ __launch_bounds__(256) void k_re_peak(re_args A) {
 struct lsdr_rate_est {
   lsdr_ctx *ctx = nullptr;
   lsdr_rate_est_cfg cfg{};
-  unsigned blocks = 0;                 // cfg.blocks with the default filled in
   lsdr_in_desc in{};
   re_args A{};
-  in_run<re_cap> run;
-  re_record *h_rec = nullptr, *d_rec = nullptr;       // pinned / device
-  float2 *d_tw = nullptr;
+  bs_host<re_record> host;
   float *d_rows = nullptr;
   float4 *d_stats = nullptr;
 };
@@ -180,31 +131,17 @@ extern "C" {
 
 void lsdr_rate_est_destroy(lsdr_rate_est *e) {
   if (!e) return;
-  (void)hipStreamSynchronize(e->ctx->stream);
-  e->run.destroy();
-  lsdr_in_free({e->d_rec, e->d_tw, e->d_rows, e->d_stats}, {e->h_rec});
+  e->host.destroy(e->ctx, {e->d_rows, e->d_stats});
   delete e;
 }
 
-static int re_build(lsdr_rate_est *e, float omega_min, float omega_max) {
-  lsdr_ctx *c = e->ctx;
+static int re_build(lsdr_rate_est *e, unsigned blocks, float omega_min, float omega_max) {
   const size_t B = (size_t)e->cfg.n_captures;
-  LSDR_HIP(hipSetDevice(c->device));
-  LSDR_TRY(e->run.create(B));
-  LSDR_HIP(hipHostMalloc((void **)&e->h_rec, B * sizeof(re_record), hipHostMallocDefault));
-  memset(e->h_rec, 0, B * sizeof(re_record));
-  LSDR_HIP(hipMalloc((void **)&e->d_rec, B * sizeof(re_record)));
-  LSDR_HIP(hipMalloc((void **)&e->d_tw, kReN * sizeof(float2)));
-  LSDR_HIP(hipMalloc((void **)&e->d_rows, B * e->blocks * kReRow * sizeof(float)));
-  LSDR_HIP(hipMalloc((void **)&e->d_stats, B * e->blocks * sizeof(float4)));
-  std::vector<float2> tw(kReN);
-  for (unsigned i = 0; i < kReN; ++i) {
-    const double a = -2.0 * M_PI * (double)i / (double)kReN;
-    tw[i] = make_float2((float)cos(a), (float)sin(a));
-  }
-  LSDR_HIP(hipMemcpy(e->d_tw, tw.data(), kReN * sizeof(float2), hipMemcpyHostToDevice));
+  LSDR_TRY(e->host.create(e->ctx, B, blocks));
+  LSDR_HIP(hipMalloc((void **)&e->d_rows, B * blocks * kReRow * sizeof(float)));
+  LSDR_HIP(hipMalloc((void **)&e->d_stats, B * blocks * sizeof(float4)));
   re_args &A = e->A;
-  A.caps = e->run.d_caps; A.tw = e->d_tw; A.rows = e->d_rows; A.stats = e->d_stats; A.rec = e->d_rec; A.row_cap = e->blocks;
+  A.caps = e->host.run.d_caps; A.tw = e->host.d_tw; A.rows = e->d_rows; A.stats = e->d_stats; A.rec = e->host.d_rec; A.row_cap = blocks;
   A.k_lo = re_k_lo(omega_min, omega_max);
   A.in_scale = e->in.in_scale; A.in_flip = e->in.in_flip;
   A.omega_min = omega_min; A.omega_max = omega_max;
@@ -213,9 +150,7 @@ static int re_build(lsdr_rate_est *e, float omega_min, float omega_max) {
 
 int lsdr_rate_est_create(lsdr_ctx *c, const lsdr_rate_est_cfg *cfg, lsdr_rate_est **out) {
   LSDR_ARG(c && cfg && out);
-  if (cfg->n_captures < 1 || cfg->n_captures > 65535) {
-    lsdr_set_error("rate_est: n_captures must be 1 to 65535 (got %d)", cfg->n_captures); return LSDR_E_ARG;
-  }
+  LSDR_TRY(bs_check_captures("rate_est", cfg->n_captures));
   lsdr_in_desc in;
   LSDR_TRY(lsdr_in_describe("rate_est", cfg->in_format, cfg->in_scale, &in));
   if (cfg->blocks > kReMaxBlocks) { lsdr_set_error("rate_est: blocks is %u, at most %u", cfg->blocks, kReMaxBlocks); return LSDR_E_ARG; }
@@ -227,8 +162,7 @@ int lsdr_rate_est_create(lsdr_ctx *c, const lsdr_rate_est_cfg *cfg, lsdr_rate_es
     if (cfg->reserved[i]) { lsdr_set_error("rate_est: lsdr_rate_est_cfg.reserved must be 0"); return LSDR_E_ARG; }
   lsdr_rate_est *e = new lsdr_rate_est();
   e->ctx = c; e->cfg = *cfg; e->in = in;
-  e->blocks = cfg->blocks ? cfg->blocks : 64u;
-  const int rc = re_build(e, lo, hi);
+  const int rc = re_build(e, cfg->blocks ? cfg->blocks : 64u, lo, hi);
   if (rc) { lsdr_rate_est_destroy(e); return rc; }
   *out = e;
   return LSDR_OK;
@@ -236,34 +170,19 @@ int lsdr_rate_est_create(lsdr_ctx *c, const lsdr_rate_est_cfg *cfg, lsdr_rate_es
 
 int lsdr_rate_est_run_async(lsdr_rate_est *e, const void *const *iq_dev, const size_t *n_samples) {
   LSDR_ARG(e && iq_dev && n_samples);
-  const unsigned B = (unsigned)e->cfg.n_captures;
-  LSDR_TRY(lsdr_in_check_each("rate_est", "tune", B, iq_dev, nullptr, n_samples, nullptr, ~(size_t)0, e->in.item_bytes));   // (any length: whole blocks of its front are read)
-  LSDR_TRY(e->run.idle("rate_est", "lsdr_rate_est_wait"));
   lsdr_ctx *c = e->ctx;
-  LSDR_HIP(hipSetDevice(c->device));
-  unsigned longest = 0;                                      // the grid is sized for it; a shorter capture's workgroups leave at once
-  for (unsigned i = 0; i < B; ++i) {
-    const size_t whole = n_samples[i] / kReN;
-    re_cap &cap = e->run.h_caps[i];
-    cap.in = reinterpret_cast<const unsigned char *>(iq_dev[i]);
-    cap.blocks = whole < e->blocks ? (unsigned)whole : e->blocks;
-    cap.pad = 0;
-    if (cap.blocks > longest) longest = cap.blocks;
-  }
-  LSDR_TRY(e->run.upload(c->stream));
+  const unsigned B = (unsigned)e->cfg.n_captures;
+  unsigned longest = 0;
+  LSDR_TRY(e->host.begin(c, "rate_est", "lsdr_rate_est_wait", iq_dev, n_samples, e->in.item_bytes, &longest));
   if (longest)
     in_dispatch(e->in.kind, [&](auto K) { hipLaunchKernelGGL(k_re_block<K()>, dim3(longest, B), dim3(256), 0, c->stream, e->A); });
   hipLaunchKernelGGL(k_re_peak, dim3(B), dim3(256), 0, c->stream, e->A);
-  LSDR_HIP(hipGetLastError());
-  LSDR_HIP(hipMemcpyAsync(e->h_rec, e->d_rec, B * sizeof(re_record), hipMemcpyDeviceToHost, c->stream));
-  return e->run.mark(c->stream);
+  return e->host.end(c);
 }
 
 int lsdr_rate_est_wait(lsdr_rate_est *e, lsdr_rate_estimate *out) {
   LSDR_ARG(e && out);
-  LSDR_TRY(e->run.wait("rate_est"));
-  memcpy(out, e->h_rec, (size_t)e->cfg.n_captures * sizeof(re_record));
-  return LSDR_OK;
+  return e->host.wait("rate_est", out);
 }
 
 }  // extern "C"

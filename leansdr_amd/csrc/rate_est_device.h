@@ -1,12 +1,12 @@
 // leansdr_amd/csrc/rate_est_device.h — the arithmetic of the symbol-rate estimator (lsdr_rate_est, include/lsdr_hip.h; kernels and host
 // side in rate_est.hip).  Plain C++ on values, callable from a kernel and from the host: the layout of a block's row, and the record of one
-// capture from its summed spectrum.  The transform is tune_est_device.h's (te_fft_stage, te_digit_reverse), the samples' conversion
+// capture from its summed spectrum.  The blocks, the transform and the reductions are block_spectrum.h's, the samples' conversion
 // capture_input.h's.
 #ifndef LSDR_RATE_EST_DEVICE_H
 #define LSDR_RATE_EST_DEVICE_H
-#include "tune_est_device.h"
+#include "block_spectrum.h"
 
-constexpr unsigned kReN = kTeN;                    // samples per block, FFT length
+constexpr unsigned kReN = kBsN;                    // samples per block, FFT length
 constexpr unsigned kReHalf = kReN / 2u;            // the last bin searched: P is symmetric
 constexpr unsigned kReRow = kReHalf + 16u;         // floats per block row: bins 0 … N/2, padded to whole 64-byte lines
 constexpr unsigned kReMaxBlocks = 256;
@@ -16,19 +16,19 @@ struct re_record { float omega, other, line, quality, corr; unsigned bin, blocks
 
 // k_lo = max(2, ⌊N/omega_max⌋): the first bin searched.  With omega_max < 2 that lies behind N/2 and only candidate b is admissible, whose
 // lowest line is 1 − 1/omega_min: k_lo = max(2, ⌊N·(1 − 1/omega_min)⌋) then.
-TE_HD unsigned re_k_lo(float omega_min, float omega_max) {
+IN_HD unsigned re_k_lo(float omega_min, float omega_max) {
   const double lowest = omega_max < 2.f ? 1.0 - 1.0 / (double)omega_min : 1.0 / (double)omega_max;
   const unsigned k = (unsigned)floor((double)kReN * lowest);
   return k < 2u ? 2u : k;
 }
-TE_HD double re_abs_sinc(double x) {
+IN_HD double re_abs_sinc(double x) {
   const double a = 3.14159265358979323846 * x;
   return a == 0.0 ? 1.0 : fabs(sin(a) / a);
 }
 
 // Steps 5 to 8 for one capture, in double: peak bin k0 with power c, neighbours l and r, the floor (mean of P over the searched bins),
 // corr = R, the blocks M.  One thread per capture runs this once; every float of the record is the one nearest to the formula's value.
-TE_HD re_record re_peak_record(unsigned k0, float l, float c, float r, float floor_, float corr, unsigned blocks, float omega_min, float omega_max) {
+IN_HD re_record re_peak_record(unsigned k0, float l, float c, float r, float floor_, float corr, unsigned blocks, float omega_min, float omega_max) {
   re_record R{};                                             // all zeros: c = 0, or no admissible candidate
   if (!(c > 0.f)) return R;
   const double lp = (double)l - (double)floor_ > 0.0 ? (double)l - (double)floor_ : 0.0;

@@ -184,6 +184,16 @@ def test_arguments(capi, ctx):
             h = C.c_void_p()
             assert word in message(lib.lsdr_tune_est_create(ctx.h, C.byref(cfg), C.byref(h)), what) and not h.value
             usable()
+        # more captures than the grid's second dimension takes: refused in front of any allocation, and an estimator made afterwards works
+        with pytest.raises(capi.LsdrError) as refusal:
+            capi.TuneEstimator(ctx, 65536)
+        assert str(refusal.value) == f"lsdr error {LSDR_E_ARG}: tune_est: n_captures must be 1 to 65535 (got 65536)"
+        after = capi.TuneEstimator(ctx, 2)
+        try:
+            assert all(_same(a, b) for a, b in zip(after.estimate([buf.ptr, None], [8 * N, 0]), want))
+        finally:
+            after.close()
+        usable()
         ptrs, lens = est._args([buf.ptr, None], [8 * N, 0])
         assert "in flight" in message(lib.lsdr_tune_est_wait(est.h, est._out), "wait with nothing in flight")
         usable()
