@@ -1297,6 +1297,80 @@ int  lsdr_ts_batch_download_wait(lsdr_ts_batch*);
 /* packets per workgroup tile: the lengths at which the kernels change their path are multiples of it */
 unsigned lsdr_ts_batch_tile(const lsdr_ts_batch*);
 
+/* ------------------------------------------------------------ TX batch: leandvbtx | leanchansim for many streams at once
+ * The mirror image of lsdr_capture_batch: n_streams transport streams in device memory, each with its own length, code rate, power, noise
+ * level and seed, become n_streams noisy captures in device memory in one set of launches.  Every stream is a pair of freshly started
+ * processes (leandvbtx.cc:79-175, leanchansim.cc:115-189):
+ *   randomizer → rs_encoder → interleaver → dvb_convol → cstln_transmitter(make_dvbs2_constellation) → fir_resampler(RRC,
+ *   normalize_power(amp/75)) → decimator [→ simple_agc] | scaler(scale) → + wgn_c(stddev) → drifter with all components zero
+ *   [→ cconverter<f32,0,u8,128,1,1>]
+ * EXACT.  Stream i's output is bit for bit what the two programs write for that stream alone — the same alone, at any position of any
+ * batch and on a reused object; a run carries nothing into the next one.  The order of operations is the reference's: AGC gain, scale,
+ * + noise, the drifter's multiplication by its table entry 0 (1, 0).
+ * PER STREAM.  fec: leandvbtx's rule "2/3 on QPSK and 64-ary runs as 4/6" applies; a rate the constellation cannot carry is refused with
+ * the code of lsdr_convol_create.  amp: leandvbtx --power, linear.  scale: leanchansim --scale (0: 1).  noise_stddev: --awgn, linear (0 is
+ * valid and still runs the adder).  seeded / seed: srand48(seed), or --deterministic's unseeded generator, as lsdr_wgn_create.
+ * THE RESULT.  packets, bytes, symbols, samples: the items that left the interleaver, that the convolutional coder took, that the mapper
+ * produced, that the object wrote.  noise_state: the drand48 state behind the last noise sample (the start state where samples is 0).
+ * noise_rounds: the rounds of the noise stage the stream took part in (1 unless its candidates ran out, 0 without samples).
+ * agc_estimated: simple_agc's estimate after the last chunk (0 without AGC).  lsdr_tx_batch_plan fills the four lengths on the host, in
+ * closed form from the blocks' consumption rules (interleaver n − 11; whole groups of the coder; lsdr_fir_resampler_run's count; the
+ * decimator; the AGC's whole 128-sample chunks), without a GPU or a context; run_async sizes its launches with it.
+ * QUEUEING.  run_async queues everything on the context's stream and returns; between run_async and wait the host reads nothing and
+ * synchronises nothing; one run in flight per object.  The number of kernel launches of a run does not depend on n_streams
+ * (lsdr_tx_batch_stats).  NOISE: wgn_c's rejection step makes positions data dependent; every stream gets a candidate budget (n·4/π plus
+ * `sigmas` standard deviations, 6 by default, lsdr_tx_batch_set_noise_margin) and a stream whose candidates run out is finished by further
+ * rounds that wait drives; the bytes do not depend on the number of rounds.
+ * OUTPUT.  The object owns the output buffers (lsdr_tx_batch_out_dev(i), 16-byte aligned, sized from max_packets at the slowest rate):
+ * `samples` items of cf32 (LSDR_IN_CF32) or cu8 (LSDR_IN_CU8, leanchansim --ou8).  download_async / download_wait copy them to the host
+ * on a stream of their own after wait; the next run's kernels wait for a pending download.
+ * OUT OF SCOPE: the drift options (--lo, --ppm, --drift*), --s16, --fill, cu8 input of leanchansim, streams continued across runs, a
+ * constellation or interp/decim per stream.
+ * LSDR_E_ARG, with a message naming tx_batch, the object (if any) left usable: n_streams outside 1 … 65535, interp or decim < 1, an
+ * out_format outside the two, rolloff or rrc_rej not finite or negative, nonzero reserved, n_packets > max_packets, a NULL pointer with
+ * packets, amp / scale / noise_stddev not finite, a code rate the constellation cannot carry, run_async with a run in flight, wait with
+ * none, a download before a wait or into too small a buffer.  LSDR_E_UNSUPPORTED: more than 1024 taps, or an interp/decim whose sample
+ * tile needs more than 16384 symbols. */
+typedef struct lsdr_tx_batch lsdr_tx_batch;
+typedef struct {
+  int n_streams;
+  size_t max_packets;
+  int cstln;                 /* every constellation lsdr_cstln_transmitter_run accepts */
+  int interp, decim;
+  float rolloff, rrc_rej;    /* 0: 0.35 and 10 */
+  int agc;
+  int out_format;            /* LSDR_IN_CF32 or LSDR_IN_CU8 */
+  int reserved[8];           /* 0 */
+} lsdr_tx_batch_cfg;
+typedef struct {
+  uint64_t n_packets;
+  int32_t fec;
+  float amp, scale, noise_stddev;
+  int32_t seeded;
+  int32_t reserved0;         /* 0 */
+  int64_t seed;
+  int32_t reserved[6];       /* 0 */
+} lsdr_tx_each;              /* 64 bytes */
+typedef struct {
+  uint64_t packets, bytes, symbols, samples, noise_state;
+  uint32_t noise_rounds;
+  float agc_estimated;
+  uint32_t reserved[4];
+} lsdr_tx_result;            /* 64 bytes */
+int  lsdr_tx_batch_create(lsdr_ctx*, const lsdr_tx_batch_cfg*, lsdr_tx_batch**);
+void lsdr_tx_batch_destroy(lsdr_tx_batch*);
+/* ts_dev: HOST array of n_streams DEVICE pointers (may be NULL where n_packets is 0); each: HOST [n_streams] */
+int  lsdr_tx_batch_run_async(lsdr_tx_batch*, const uint8_t *const *ts_dev, const lsdr_tx_each *each);
+int  lsdr_tx_batch_wait(lsdr_tx_batch*, lsdr_tx_result *results /* [n_streams], may be NULL */);
+const void *lsdr_tx_batch_out_dev(const lsdr_tx_batch*, int i);            /* NULL: i out of range */
+const lsdr_tx_result *lsdr_tx_batch_results_dev(const lsdr_tx_batch*);     /* [n_streams], valid after wait */
+int  lsdr_tx_batch_download_async(lsdr_tx_batch*, void *const *host /* [n_streams] HOST pointers */, size_t cap_bytes);
+int  lsdr_tx_batch_download_wait(lsdr_tx_batch*);
+int  lsdr_tx_batch_stats(const lsdr_tx_batch*, unsigned *launches_last_run, unsigned long long *runs);
+int  lsdr_tx_batch_set_noise_margin(lsdr_tx_batch*, float sigmas);         /* a negative value makes round 1 fall short (tests) */
+int  lsdr_tx_batch_plan(const lsdr_tx_batch_cfg*, const lsdr_tx_each*, lsdr_tx_result*);   /* host only */
+float lsdr_db_to_amplitude(double db);                                     /* expf(logf(10)*db/20): how both apps parse --power and --awgn */
+
 #ifdef __cplusplus
 }
 #endif

@@ -527,6 +527,41 @@ _sig("lsdr_ts_batch_download_async", C.c_int, [vp, vp, c_sz])
 _sig("lsdr_ts_batch_download_wait", C.c_int, [vp])
 _sig("lsdr_ts_batch_tile", C.c_uint, [vp])
 
+
+class TxBatchCfg(C.Structure):
+    """lsdr_tx_batch_cfg"""
+    _fields_ = [("n_streams", C.c_int), ("max_packets", C.c_size_t), ("cstln", C.c_int), ("interp", C.c_int), ("decim", C.c_int),
+                ("rolloff", c_f), ("rrc_rej", c_f), ("agc", C.c_int), ("out_format", C.c_int), ("reserved", C.c_int * 8)]
+
+
+class TxEach(C.Structure):
+    """lsdr_tx_each: one stream of a run (64 bytes)."""
+    _fields_ = [("n_packets", C.c_uint64), ("fec", C.c_int32), ("amp", c_f), ("scale", c_f), ("noise_stddev", c_f), ("seeded", C.c_int32),
+                ("reserved0", C.c_int32), ("seed", C.c_int64), ("reserved", C.c_int32 * 6)]
+
+
+class TxResult(C.Structure):
+    """lsdr_tx_result (64 bytes)."""
+    _fields_ = [(k, C.c_uint64) for k in ("packets", "bytes", "symbols", "samples", "noise_state")] + \
+               [("noise_rounds", C.c_uint32), ("agc_estimated", c_f), ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+_sig("lsdr_tx_batch_create", C.c_int, [vp, C.POINTER(TxBatchCfg), C.POINTER(vp)])
+_sig("lsdr_tx_batch_destroy", None, [vp])
+_sig("lsdr_tx_batch_run_async", C.c_int, [vp, vp, C.POINTER(TxEach)])
+_sig("lsdr_tx_batch_wait", C.c_int, [vp, C.POINTER(TxResult)])
+_sig("lsdr_tx_batch_out_dev", vp, [vp, C.c_int])
+_sig("lsdr_tx_batch_results_dev", vp, [vp])
+_sig("lsdr_tx_batch_download_async", C.c_int, [vp, vp, c_sz])
+_sig("lsdr_tx_batch_download_wait", C.c_int, [vp])
+_sig("lsdr_tx_batch_stats", C.c_int, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong)])
+_sig("lsdr_tx_batch_set_noise_margin", C.c_int, [vp, c_f])
+_sig("lsdr_tx_batch_plan", C.c_int, [C.POINTER(TxBatchCfg), C.POINTER(TxEach), C.POINTER(TxResult)])
+_sig("lsdr_db_to_amplitude", c_f, [C.c_double])
+
 #: decode_estimated's default threshold on `quality`: the geometric mean of what Gaussian noise alone reaches (3.1) and the weakest of the
 #: test captures (347), rounded (DESIGN.md §4.8)
 TUNE_MIN_QUALITY = 30.0
@@ -2654,3 +2689,125 @@ class TxChain:
             self.agc_hold = y[cons:]
             y = z
         return y
+
+
+# ---- leandvbtx | leanchansim for many streams (lsdr_tx_batch) ----------------------------
+def db_to_amplitude(db):
+    """How leandvbtx --power and leanchansim --awgn read their argument: expf(logf(10)·db/20)."""
+    return float(lib.lsdr_db_to_amplitude(float(db)))
+
+
+class TxBatch:
+    """lsdr_tx_batch: n_streams transport streams, each with its own length, code rate, power, scale, noise level and seed, become
+    n_streams noisy captures in device memory in one set of launches; every capture is bit for bit what leandvbtx | leanchansim write
+    for that stream alone (include/lsdr_hip.h).  `ptrs()` and `lengths()` are what the batch decoders and estimators take.
+    ctx None: no device object, only `plan`."""
+
+    def __init__(self, ctx, n_streams, max_packets, interp=2, decim=1, cstln=QPSK, agc=False, rolloff=0.35, rrc_rej=10.0,
+                 out_format=IN_CF32):
+        self.ctx, self.n, self.h = ctx, int(n_streams), None
+        cfg = TxBatchCfg()
+        cfg.n_streams, cfg.max_packets, cfg.cstln, cfg.interp, cfg.decim = self.n, int(max_packets), int(cstln), int(interp), int(decim)
+        cfg.rolloff, cfg.rrc_rej, cfg.agc, cfg.out_format = rolloff, rrc_rej, 1 if agc else 0, int(out_format)
+        self.cfg, self.out_format = cfg, int(out_format)
+        self._res = (TxResult * max(self.n, 1))()
+        self._last = []
+        self._keep = []
+        if ctx is not None:
+            h = vp()
+            check(lib.lsdr_tx_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
+            self.h = h
+
+    def close(self):
+        if self.h:
+            lib.lsdr_tx_batch_destroy(self.h)
+            self.h = None
+        for d in self._keep:
+            d.free()
+        self._keep = []
+
+    @staticmethod
+    def each(n_packets=0, fec=FEC12, amp=None, power_db=None, scale=0.0, awgn_db=None, noise_stddev=None, seed=None):
+        """One stream's lsdr_tx_each.  amp | power_db (default amp 1), noise_stddev | awgn_db (default 0), seed None: --deterministic."""
+        e = TxEach()
+        e.n_packets, e.fec, e.scale = int(n_packets), int(fec), scale
+        e.amp = (1.0 if power_db is None else db_to_amplitude(power_db)) if amp is None else amp
+        e.noise_stddev = (0.0 if awgn_db is None else db_to_amplitude(awgn_db)) if noise_stddev is None else noise_stddev
+        e.seeded, e.seed = (0, 0) if seed is None else (1, int(seed))
+        return e
+
+    def plan(self, each, n_packets=None):
+        """The four lengths of one stream (dict(packets, bytes, symbols, samples)), on the host: no GPU, no context."""
+        e = each if isinstance(each, TxEach) else self.each(**each)
+        if n_packets is not None:
+            e.n_packets = int(n_packets)
+        r = TxResult()
+        check(lib.lsdr_tx_batch_plan(C.byref(self.cfg), C.byref(e), C.byref(r)))
+        return {k: int(getattr(r, k)) for k in ("packets", "bytes", "symbols", "samples")}
+
+    def set_noise_margin(self, sigmas):
+        check(lib.lsdr_tx_batch_set_noise_margin(self.h, sigmas))
+
+    def stats(self):
+        a, b = C.c_uint(), C.c_ulonglong()
+        check(lib.lsdr_tx_batch_stats(self.h, C.byref(a), C.byref(b)))
+        return dict(launches_last_run=a.value, runs=b.value)
+
+    def run_async(self, ts, each):
+        """Queues one run.  ts: per stream a numpy array of 188-byte packets (uploaded here), or (device pointer, n_packets); each: per
+        stream a TxEach or the keyword arguments of `each` (n_packets is taken from ts)."""
+        if len(ts) != self.n or len(each) != self.n:
+            raise LsdrError(f"tx batch: {len(ts)} streams and {len(each)} records for {self.n} streams")
+        keep = []                                        # this run's uploads; the last run's are freed once this one is accepted
+        arr = (TxEach * self.n)()
+        ptrs = (vp * self.n)()
+        for i, (t, e) in enumerate(zip(ts, each)):
+            if isinstance(t, tuple):
+                ptr, npk = t
+                ptr = ptr.value if isinstance(ptr, vp) else ptr
+            else:
+                a = np.ascontiguousarray(t, np.uint8).reshape(-1, 188)
+                npk, ptr = len(a), None
+                if npk:
+                    d = self.ctx.upload(a)
+                    keep.append(d)
+                    ptr = d.ptr.value if isinstance(d.ptr, vp) else d.ptr
+            arr[i] = e if isinstance(e, TxEach) else self.each(**e)
+            arr[i].n_packets = int(npk)
+            ptrs[i] = ptr
+        rc = lib.lsdr_tx_batch_run_async(self.h, ptrs, arr)
+        for d in (keep if rc else self._keep):           # refused (a run may be in flight): the last run's uploads stay
+            d.free()
+        if not rc:
+            self._keep = keep
+        check(rc)
+
+    def wait(self):
+        check(lib.lsdr_tx_batch_wait(self.h, self._res))
+        self._last = [r.as_dict() for r in self._res[:self.n]]
+        return self._last
+
+    def run(self, ts, each):
+        self.run_async(ts, each)
+        return self.wait()
+
+    def ptrs(self):
+        return [lib.lsdr_tx_batch_out_dev(self.h, i) for i in range(self.n)]
+
+    def lengths(self):
+        return [int(r["samples"]) for r in self._last]
+
+    def results_ptr(self):
+        return lib.lsdr_tx_batch_results_dev(self.h)
+
+    def download_all(self):
+        """Every stream of the last run: complex64 arrays, or uint8 [n, 2] with IN_CU8."""
+        u8 = self.out_format == IN_CU8
+        cap = max(self.lengths() + [1])
+        bufs = [np.empty((cap, 2), np.uint8) if u8 else np.empty(cap, np.complex64) for _ in range(self.n)]
+        check(lib.lsdr_tx_batch_download_async(self.h, (vp * self.n)(*[b.ctypes.data for b in bufs]), bufs[0].nbytes))
+        check(lib.lsdr_tx_batch_download_wait(self.h))
+        return [b[:n] for b, n in zip(bufs, self.lengths())]
+
+    def download(self, i):
+        return self.download_all()[i]

@@ -18,38 +18,12 @@
 // pipe size); the ABI takes that chunk length, a lane walks one chunk with the reference's float/double/integer conversions
 // spelled out (x86 "integer indefinite" on overflow/NaN), and a parallel pass applies the rotation.
 #include "lsdr_internal.h"
+#include "tx_batch_device.h"   // the drand48 jump, the logf restatement, the x86 conversions: shared with tx_batch.hip
 
 namespace {
 
-constexpr unsigned long long kLcgA = 0x5DEECE66DULL, kLcgC = 0xBULL, kLcgMask = 0xFFFFFFFFFFFFULL;
 constexpr int kWgnBlock = 256, kWgnPairs = 16;                    // candidate pairs per thread
 constexpr unsigned kWgnPerBlock = kWgnBlock * kWgnPairs;
-
-struct lcg_pow { unsigned long long a[48], c[48]; };               // X_{k+2^b} = a[b]·X_k + c[b]  (mod 2^48)
-struct logf_tab { double invc[16], logc[16]; };
-
-__device__ __forceinline__ unsigned long long lcg_jump(const lcg_pow &p, unsigned long long x, unsigned long long k) {
-  for (int b = 0; b < 48 && (k >> b); ++b)
-    if ((k >> b) & 1) x = (p.a[b] * x + p.c[b]) & kLcgMask;
-  return x;
-}
-__device__ __forceinline__ double lcg_next(unsigned long long &x) {
-  x = (x * kLcgA + kLcgC) & kLcgMask;
-  return (double)x * 0x1p-48;
-}
-// glibc 2.35 logf for positive normal x (sysdeps/ieee754/flt-32/e_logf.c)
-__device__ __forceinline__ float glibc_logf(const logf_tab &t, float x) {
-  const unsigned ix = __float_as_uint(x);
-  if (ix == 0x3f800000u) return 0.f;
-  const unsigned tmp = ix - 0x3f330000u;
-  const int i = (tmp >> 19) % 16, k = (int)tmp >> 23;
-  const unsigned iz = ix - (tmp & (0x1ffu << 23));
-  const double z = (double)__uint_as_float(iz), r = z * t.invc[i] - 1, y0 = t.logc[i] + (double)k * 0x1.62e42fefa39efp-1, r2 = r * r;
-  double y = 0x1.5575b0be00b6ap-2 * r + -0x1.ffffef20a4123p-2;
-  y = -0x1.00ea348b88334p-2 * r2 + y;
-  y = y * r2 + (y0 + r);
-  return (float)y;
-}
 
 // Candidate pairs [first, first+count) of the stream that starts at state *x0; thread t of block b owns pairs
 // (b·256 + t)·kWgnPairs … .  Pass 1: accepted pairs per block.
@@ -157,12 +131,6 @@ __global__ __launch_bounds__(256) void k_add(const float2 *a, const float2 *b, u
     out[i] = make_float2(a[i].x + b[i].x, a[i].y + b[i].y);
 }
 
-// cvttss2si / cvttsd2si: the "integer indefinite" value when the source is NaN or out of range
-__device__ __forceinline__ int x86_f2i(float v) { return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000; }
-__device__ __forceinline__ long long x86_d2l(double v) {
-  return (v >= -9223372036854775808.0 && v < 9223372036854775808.0) ? (long long)v : (long long)0x8000000000000000ULL;
-}
-
 __global__ __launch_bounds__(256) void k_cconv_f32_u8(const float2 *in, unsigned long long n, uchar2 *out) {
   const unsigned long long stride = (unsigned long long)gridDim.x * 256;
   for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
@@ -262,26 +230,10 @@ int lsdr_wgn_create(lsdr_ctx *c, int seeded, long seed, lsdr_wgn **out) {
   lsdr_wgn *w = new lsdr_wgn();
   w->ctx = c;
   lcg_pow p;
-  p.a[0] = kLcgA; p.c[0] = kLcgC;
-  for (int b = 1; b < 48; ++b) {   // (a,c)∘(a,c): X → a·(a·X + c) + c
-    p.a[b] = (p.a[b - 1] * p.a[b - 1]) & kLcgMask;
-    p.c[b] = (p.a[b - 1] * p.c[b - 1] + p.c[b - 1]) & kLcgMask;
-  }
-  // glibc 2.35 sysdeps/ieee754/flt-32/e_logf_data.c (N = 16): {1/c, log c} for the 16 sub-intervals of [0.7, 1.4)
-  static const double tab[16][2] = {
-      {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2},
-      {0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2},  {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3},
-      {0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3}, {0x1.25e227b0b8eap+0, -0x1.1aa2bc79c81p-3},
-      {0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4}, {0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4},
-      {0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5}, {0x1p+0, 0x0p+0},
-      {0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5},  {0x1.ca4b31f026aap-1, 0x1.c5e53aa362eb4p-4},
-      {0x1.b2036576afce6p-1, 0x1.526e57720db08p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.bc2860d22477p-3},
-      {0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2},  {0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2},
-  };
+  lsdr_lcg_pow_fill(p);
   logf_tab lt;
-  for (int i = 0; i < 16; ++i) { lt.invc[i] = tab[i][0]; lt.logc[i] = tab[i][1]; }
-  // glibc keeps the drand48 state in zeroed static storage: an unseeded process starts from X = 0; srand48(s): X = s<<16 | 0x330E
-  const unsigned long long x0[3] = {seeded ? ((((unsigned long long)(unsigned)seed) << 16) | 0x330E) : 0ULL, 0, 0};
+  lsdr_logf_tab_fill(lt);
+  const unsigned long long x0[3] = {lsdr_drand48_start(seeded, seed), 0, 0};
   LSDR_HIP(hipMalloc((void **)&w->d_state, sizeof(x0)));
   LSDR_HIP(hipMalloc((void **)&w->d_pow, sizeof(p)));
   LSDR_HIP(hipMalloc((void **)&w->d_logf, sizeof(lt)));

@@ -14,6 +14,7 @@
 // over the chunks).  Bit-exact against the oracle, which is pinned to the reference blocks and to `leandvbtx` itself.
 #include <mutex>
 #include "lsdr_internal.h"
+#include "tx_batch_device.h"   // gf_tab: shared with tx_batch.hip
 
 namespace {
 
@@ -25,8 +26,6 @@ __global__ __launch_bounds__(256) void k_randomize(const unsigned char *in, unsi
   for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < nbytes; i += stride)
     out[i] = in[i] ^ pattern[(pos0 + i) % 1504u];
 }
-
-struct gf_tab { unsigned char exp[512], log[256], G[17]; };
 
 // rs_engine::encode (rs.h:141-167): one thread per packet, tables in LDS.
 __global__ __launch_bounds__(64) void k_rs_encode(const unsigned char *in, unsigned long long npackets, const gf_tab *tab,
