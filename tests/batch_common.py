@@ -1,6 +1,7 @@
 """Shared helpers of the batch decoders' tests (lsdr_capture_batch in its engines and formats, lsdr_hs_batch): the synthetic captures, the
 reference binary's TS for them, the rule a batch's TS is compared with it by, the input variants of the exactness tests, and the FEC tail
-driven by the host as the checker of the device-resident one.
+driven by the host as the checker of the device-resident one — behind deconvol_sync (_chain_reference) and behind viterbi_sync
+(_stage_reference), at any code rate — and the captures, variants, references and comparison rule of the punctured-rate tests.
 
 The reference binary (oracle/_ref/leandvb) is required by run_reference: where it is missing its callers FAIL.
 """
@@ -18,6 +19,12 @@ sys.path.insert(0, ROOT)
 
 REFBIN = os.path.join(ROOT, "oracle", "_ref", "leandvb")
 REF_U8 = ("--u8", "-f", "2400e3", "--sr", "2000e3", "--cr", "1/2")       # leandvb's arguments for the cu8 captures below
+CR = {0: "1/2", 1: "2/3", 3: "3/4", 4: "5/6", 5: "7/8"}                  # LSDR_FEC12 … LSDR_FEC78 as leandvb's --cr takes them
+
+
+def ref_args(rate, *extra):
+    """leandvb's arguments for a cu8 capture at 1.2 samples per symbol and code rate `rate`."""
+    return REF_U8[:-1] + (CR[rate],) + tuple(extra)
 
 
 @functools.lru_cache(maxsize=None)
@@ -43,6 +50,17 @@ def rotate_u8(iq, quarter_turns):
     return np.ascontiguousarray(a).reshape(-1)
 
 
+def with_burst(base, start, burst, rng):
+    """The capture with `burst` samples of garbage from sample `start` on."""
+    hit = base.copy()
+    hit[2 * start: 2 * (start + burst)] = rng.integers(100, 156, 2 * burst, dtype=np.uint8)
+    return hit
+
+
+def noise_only(n, rng):
+    return rng.integers(96, 160, 2 * n, dtype=np.uint8).astype(np.uint8)
+
+
 def six_variants(base, n, burst):
     """[(name, IQ)] of an n-sample capture: as generated; rotated by 90, 180 and 270 degrees; `burst` samples of garbage in the middle (the
     lock drops, then comes back); noise only (never locks)."""
@@ -50,11 +68,60 @@ def six_variants(base, n, burst):
     variants = [("as generated", base)]
     for q in (1, 2, 3):
         variants.append((f"rotated {90 * q} deg", rotate_u8(base, q)))
-    hit = base.copy()
-    hit[2 * (n // 2): 2 * (n // 2 + burst)] = rng.integers(100, 156, 2 * burst, dtype=np.uint8)
-    variants.append(("garbage burst in the middle", hit))
-    variants.append(("noise only (never locks)", rng.integers(96, 160, 2 * n, dtype=np.uint8).astype(np.uint8)))
+    variants.append(("garbage burst in the middle", with_burst(base, n // 2, burst, rng)))
+    variants.append(("noise only (never locks)", noise_only(n, rng)))
     return variants
+
+
+@functools.lru_cache(maxsize=None)
+def rate_capture(rate, n_packets, noise_db=17.5):
+    """A cu8 capture at 1.2 samples per symbol and code rate `rate`, made on the CPU by the oracle's leandvbtx | leanchansim (tx_chain with
+    agc, amplitude 75; --awgn noise_db --ou8, seed rate + 1), packets numbered from 1000·rate: (IQ items, the set of transmitted packets)."""
+    import pyoracle
+    from leansdr_amd import synth_dvbs
+    o = pyoracle.Oracle()
+    ts = synth_dvbs.ts_packets(n_packets, start=1000 * rate)
+    y = o.tx_chain(ts, interp=6, decim=5, amp=75, agc=True, cstln=1, rate=rate)
+    iq = o.chansim(y, awgn_db=noise_db, scale=1, ou8=True, seed=rate + 1)
+    return np.ascontiguousarray(iq, np.uint8).reshape(-1), {bytes(p) for p in ts}
+
+
+RATE_VARIANTS = ("as generated", "rotated 90 deg", "rotated 180 deg", "rotated 270 deg", "first 1201 samples dropped",
+                 "first 2402 samples dropped", "first 3603 samples dropped", "garbage burst", "noise only")
+
+
+def rate_variant_of(iq, name):
+    """One of RATE_VARIANTS of a capture: as generated; rotated by 90, 180 and 270 degrees; its first 1201, 2402 and 3603 samples dropped
+    (other symbol phases of the puncturing pattern); n/20 samples of garbage from 3n/4 on; noise only, as long as the capture."""
+    n, k = len(iq) // 2, RATE_VARIANTS.index(name)
+    if k < 4:
+        return rotate_u8(iq, k) if k else iq
+    if k < 7:
+        return np.ascontiguousarray(iq[2 * 1201 * (k - 3):])
+    rng = np.random.default_rng(5)
+    hit = with_burst(iq, 3 * n // 4, n // 20, rng)              # (the noise is drawn behind the burst's, as six_variants draws it)
+    return hit if k == 7 else noise_only(n, rng)
+
+
+def rate_variants(iq):
+    """[(name, IQ)] of a capture, RATE_VARIANTS in their order."""
+    return [(name, rate_variant_of(iq, name)) for name in RATE_VARIANTS]
+
+
+def rate_variant(rate, n_packets, name):
+    return rate_variant_of(rate_capture(rate, n_packets)[0], name)
+
+
+@functools.lru_cache(maxsize=None)
+def rate_reference_ts(rate, n_packets, name, args):
+    """The reference binary's TS, under the arguments `args` (a tuple), for the variant `name` of rate_capture(rate, n_packets)."""
+    return run_reference(args, rate_variant(rate, n_packets, name))
+
+
+def rate_references(keys):
+    """rate_reference_ts(*key) of every key, eight processes at a time, each once per session."""
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        return list(ex.map(lambda k: rate_reference_ts(*k), keys))
 
 
 def run_reference(args, items):
@@ -104,6 +171,35 @@ def check_against_reference(got, ref, sent, min_ref_packets, name, sent_from_fir
     same = got == ref
     print(f"{name}: {len(pk)} packets, reference {len(rpk)}, compared {m}, first compared at {i0}, whole TS identical: {same}")
     return same
+
+
+LATE_MAX = 3 * 8 * 8      # packets: one hypothesis of the reference's search — 3 next_sync cycles × 8 bit phases × 8 packets (dvb.h:755-779)
+
+
+def check_from_first_common_packet(got, ref, sent, name):
+    """The rule for captures whose lock instant is far from the start (punctured rates: the symbol phase is found through next_sync()).
+    The first packet of the batch's TS from index bench_c1.SKIP_ACQ on that also occurs in the reference's TS pairs the two; from there
+    on they are identical packet for packet until one ends, at most 16 of the reference's last packets are not reached, at least 500 are
+    compared, every compared packet was transmitted, and the batch is at most LATE_MAX packets later than the reference in front of the
+    pair (earlier is allowed).  Returns dict(late, batch, reference, compared)."""
+    import bench_c1
+    rpk, pk = packets(ref), packets(got)
+    assert len(ref) % 188 == 0 and len(got) % 188 == 0, name
+    where = {}
+    for j, p in enumerate(rpk):
+        where.setdefault(p, j)
+    i0 = next((i for i in range(bench_c1.SKIP_ACQ, len(pk)) if pk[i] in where), None)
+    assert i0 is not None, f"{name}: no packet of the batch's TS ({len(pk)} packets) is in the reference's ({len(rpk)})"
+    j0 = where[pk[i0]]
+    m = min(len(pk) - i0, len(rpk) - j0)
+    late = j0 - i0
+    print(f"{name}: {len(pk)} packets, reference {len(rpk)}, pair at {i0} / {j0}, compared {m}, late {late}")
+    assert pk[i0:i0 + m] == rpk[j0:j0 + m], f"{name}: differs from the reference behind the first common packet"
+    assert len(rpk) - j0 - m <= 16, f"{name}: {len(rpk) - j0 - m} of the reference's last packets not reached"
+    assert m >= 500, f"{name}: only {m} packets compared"
+    assert all(p in sent for p in pk[i0:i0 + m]), f"{name}: a packet that was never transmitted"
+    assert late <= LATE_MAX, f"{name}: the batch locks {late} packets behind the reference"
+    return dict(late=late, batch=len(pk), reference=len(rpk), compared=m)
 
 
 def decode_batch(ctx, iqs, n_samples, make, obj=None):
@@ -164,3 +260,60 @@ class HostTail:
             d.free()
         self.msync.close(); self.derand.close()
         return out
+
+
+def _chain_reference(capi, ctx, words, nsym, byte_cap, window, rate=0):
+    """deconvol_sync in front of HostTail, with mpeg_sync's next_sync() requests passed on.  `words`: the packed decisions on the device.
+    Returns (deconvolved bytes, mpeg bytes, TS bytes, stats)."""
+    dec, t = capi.Deconv(ctx, rate), HostTail(capi, ctx, byte_cap)
+    pos = calls = 0
+
+    def next_sync():
+        nonlocal calls
+        dec.next_sync()
+        calls += 1
+
+    while True:
+        cap = byte_cap - t.bw if t.msync.locked else min(window, byte_cap - t.bw)
+        c, p = dec.run_dev_hs2(words, pos, nsym - pos, t.d_bytes.at(t.bw), cap)
+        if not p:
+            break
+        pos += c; t.bw += p
+        t.sync(next_sync)
+    want_bytes, want_mpeg, want_ts, st = t.finish()
+    dec.close()
+    return want_bytes, want_mpeg, want_ts, dict(st, next_sync=calls)
+
+
+def _stage_reference(capi, ctx, soft_ptr, nsym, rate=0):
+    """What the one-block-per-call C ABI makes of the soft symbols at soft_ptr when the host drives it: a fresh lsdr_viterbi_run in front of
+    HostTail (nobody to call next_sync() on).  2/3 runs as 4/6 on QPSK, as leandvb.cc:533-537 has it.  Returns (bytes, mpeg bytes, TS, stats)."""
+    byte_cap = nsym // 4 + 65536
+    vit, t = capi.Viterbi(ctx, capi.QPSK, capi.FEC46 if rate == capi.FEC23 else rate), HostTail(capi, ctx, byte_cap)
+    done = 0
+    while True:                                   # (one call takes every chunk that fits; the next one finds nothing)
+        c, p = vit.run_dev(C.c_void_p(soft_ptr + 4 * done), nsym - done, t.d_bytes.at(t.bw), byte_cap - t.bw)
+        if not c:
+            break
+        done += c; t.bw += p
+    t.sync()
+    want_bytes, want_mpeg, want_ts, st = t.finish()
+    st["sync"] = int(vit.current_sync)
+    vit.close()
+    return want_bytes, want_mpeg, want_ts, st
+
+
+def _assert_stages_exact(capi, ctx, cb, res, ts, names, rate=0):
+    for i, name in enumerate(names):
+        r = res[i]
+        want_bytes, want_mpeg, want_ts, st = _stage_reference(capi, ctx, cb.soft_ptr(i), r["symbols"], rate)
+        got_bytes = cb.stage_bytes(i, "deconv", r["bytes_deconv"])
+        got_mpeg = cb.stage_bytes(i, "mpeg", r["bytes_mpeg"])
+        assert r["bytes_deconv"] == len(want_bytes) and got_bytes.tobytes() == want_bytes.tobytes(), name
+        assert r["alignment"] == st["sync"], (name, r, st)
+        assert r["bytes_mpeg"] == len(want_mpeg) and got_mpeg.tobytes() == want_mpeg.tobytes(), name
+        assert r["rs_packets"] == st["npk"] and r["locked"] == st["locked"] and r["rs_bit_errors"] == st["errs"], (name, r, st)
+        assert r["next_sync_calls"] == 0, (name, r)
+        assert ts[i] == want_ts.tobytes(), name
+        vs = cb.viterbi_stats(i)
+        assert vs["bytes"] == r["bytes_deconv"] and vs["current_sync"] == r["alignment"], (name, vs, r)

@@ -13,7 +13,7 @@ shared launches with every data-dependent count on the device.
 """
 import numpy as np
 import pytest
-from batch_common import HostTail, six_variants
+from batch_common import _chain_reference, six_variants
 
 pytestmark = pytest.mark.gpu
 
@@ -45,29 +45,6 @@ def test_every_capture_decodes_to_the_reference_ts(capi, anf, tile):
         assert n == 2 * len(job.groups) and ms > 0
     finally:
         job.close()
-
-
-def _chain_reference(capi, ctx, words, nsym, byte_cap, window):
-    """deconvol_sync in front of batch_common.HostTail, with mpeg_sync's next_sync() requests passed on.  `words`: the packed decisions on
-    the device.  Returns (deconvolved bytes, mpeg bytes, TS bytes, stats)."""
-    dec, t = capi.Deconv(ctx, capi.FEC12), HostTail(capi, ctx, byte_cap)
-    pos = calls = 0
-
-    def next_sync():
-        nonlocal calls
-        dec.next_sync()
-        calls += 1
-
-    while True:
-        cap = byte_cap - t.bw if t.msync.locked else min(window, byte_cap - t.bw)
-        c, p = dec.run_dev_hs2(words, pos, nsym - pos, t.d_bytes.at(t.bw), cap)
-        if not p:
-            break
-        pos += c; t.bw += p
-        t.sync(next_sync)
-    want_bytes, want_mpeg, want_ts, st = t.finish()
-    dec.close()
-    return want_bytes, want_mpeg, want_ts, dict(st, next_sync=calls)
 
 
 @pytest.mark.parametrize("window", [0, 65536])

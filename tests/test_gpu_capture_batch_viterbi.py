@@ -11,11 +11,9 @@ deinterleaver → rs_decoder → derandomizer), in shared launches.
 
 The reference binary (oracle/_ref/leandvb) is required: where it is missing these tests FAIL.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
-from batch_common import REF_U8, HostTail, capture, check_against_reference, decode_batch, references, six_variants
+from batch_common import REF_U8, _assert_stages_exact, capture, check_against_reference, decode_batch, references, six_variants
 
 pytestmark = pytest.mark.gpu
 
@@ -118,40 +116,6 @@ def test_soft_symbols_against_the_oracle_chain(capi, ctx, oracle, anf, tile, cw_
         cb.close()
         for b in bufs:
             b.free()
-
-
-def _stage_reference(capi, ctx, soft_ptr, nsym):
-    """What the one-block-per-call C ABI makes of the soft symbols at soft_ptr when the host drives it: a fresh lsdr_viterbi_run in front of
-    batch_common.HostTail (nobody to call next_sync() on).  Returns (bytes, mpeg bytes, TS, stats)."""
-    byte_cap = nsym // 4 + 65536
-    vit, t = capi.Viterbi(ctx, capi.QPSK, capi.FEC12), HostTail(capi, ctx, byte_cap)
-    done = 0
-    while True:                                   # (one call takes every chunk that fits; the next one finds nothing)
-        c, p = vit.run_dev(C.c_void_p(soft_ptr + 4 * done), nsym - done, t.d_bytes.at(t.bw), byte_cap - t.bw)
-        if not c:
-            break
-        done += c; t.bw += p
-    t.sync()
-    want_bytes, want_mpeg, want_ts, st = t.finish()
-    st["sync"] = int(vit.current_sync)
-    vit.close()
-    return want_bytes, want_mpeg, want_ts, st
-
-
-def _assert_stages_exact(capi, ctx, cb, res, ts, names):
-    for i, name in enumerate(names):
-        r = res[i]
-        want_bytes, want_mpeg, want_ts, st = _stage_reference(capi, ctx, cb.soft_ptr(i), r["symbols"])
-        got_bytes = cb.stage_bytes(i, "deconv", r["bytes_deconv"])
-        got_mpeg = cb.stage_bytes(i, "mpeg", r["bytes_mpeg"])
-        assert r["bytes_deconv"] == len(want_bytes) and got_bytes.tobytes() == want_bytes.tobytes(), name
-        assert r["alignment"] == st["sync"], (name, r, st)
-        assert r["bytes_mpeg"] == len(want_mpeg) and got_mpeg.tobytes() == want_mpeg.tobytes(), name
-        assert r["rs_packets"] == st["npk"] and r["locked"] == st["locked"] and r["rs_bit_errors"] == st["errs"], (name, r, st)
-        assert r["next_sync_calls"] == 0, (name, r)
-        assert ts[i] == want_ts.tobytes(), name
-        vs = cb.viterbi_stats(i)
-        assert vs["bytes"] == r["bytes_deconv"] and vs["current_sync"] == r["alignment"], (name, vs, r)
 
 
 def test_viterbi_stage_and_tail_are_exact_on_the_objects_own_soft_symbols(capi, ctx):

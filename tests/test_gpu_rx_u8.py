@@ -163,28 +163,40 @@ def test_packed_hard_output_is_the_soft_output_s_symbol_field(capi, ctx, capture
     soft.close(); hard.close(); d.free(); o_soft.free(); o_hard.free()
 
 
-@pytest.mark.parametrize("rate", [0, 3])
+@pytest.mark.parametrize("rate", [0, 1, 3, 4, 5])
 @pytest.mark.parametrize("offset", [0, 9])
-def test_deconv_on_packed_symbols(capi, ctx, rate, offset):
-    """lsdr_deconv_run_hs2 == lsdr_deconv_run on the same hard symbols, call by call (carried shift registers, next_sync())."""
+def test_deconv_on_packed_symbols(capi, ctx, oracle, rate, offset):
+    """lsdr_deconv_run_hs2 == lsdr_deconv_run on the same hard symbols, call by call (carried shift registers, next_sync() — one behind
+    the second call, four more behind the third: the wrap to alignment 0 with a symbol skipped, dvb.h:185-193), at every code rate; and
+    the packed path's bytes and consumed counts are the oracle's deconvol_sync's, driven through the same calls."""
+    import ctypes as C
     rng = np.random.default_rng(11 + rate)
     n = 300000
     hs = rng.integers(0, 4, n).astype(np.uint8)
     sym = np.zeros(n, capi.SOFTSYM); sym["symbol"] = hs; sym["cost"] = rng.integers(-500, 500, n)
+    osym = np.zeros(n, po.SOFTSYM); osym["symbol"] = hs
     d_soft, d_words = ctx.upload(sym), ctx.upload(capi.hs2_pack(hs, offset))
     a, b = capi.Deconv(ctx, rate), capi.Deconv(ctx, rate)
-    oa, ob = ctx.alloc(n), ctx.alloc(n)
+    h = oracle.lib.lo_deconv_new(rate, 0)
+    oa, ob, want = ctx.alloc(n), ctx.alloc(n), np.empty(n + 64, np.uint8)
     pos = 0
+    got_all, want_all = [], []
     for k, piece in enumerate((70000, 63, 5000, 100001, 1 << 30)):
         m = min(piece, n - pos)
         ca, pa = a.run_dev(d_soft.at(4 * pos), m, oa.ptr, n)
         cb, pb = b.run_dev_hs2(d_words.ptr, offset + pos, m, ob.ptr, n)
         assert (ca, pa) == (cb, pb)
         assert bits_equal(ctx.download(oa, np.uint8, pa), ctx.download(ob, np.uint8, pb)), k
+        co = C.c_size_t()
+        po_n = oracle.lib.lo_deconv_run(h, osym[pos:].ctypes.data, m, want.ctypes.data, n, C.byref(co))
+        assert (cb, pb) == (co.value, po_n), (k, cb, pb, co.value, po_n)
+        got_all.append(ctx.download(ob, np.uint8, pb)); want_all.append(want[:po_n].copy())
         pos += ca
-        if k == 1:
-            a.next_sync(); b.next_sync()
+        for _ in range({1: 1, 2: 4}.get(k, 0)):
+            a.next_sync(); b.next_sync(); oracle.lib.lo_deconv_next_sync(h)
+    oracle.lib.lo_deconv_free(h)
     assert pos > n - 200
+    assert bits_equal(np.concatenate(got_all), np.concatenate(want_all))
     a.close(); b.close(); d_soft.free(); d_words.free(); oa.free(); ob.free()
 
 

@@ -122,9 +122,10 @@ def test_8psk23_three_seeds_one_batch(capi, ctx, oracle, vit_kernel):
     check_streams(oracle, got, syms, 2, 1)
 
 
-@pytest.mark.parametrize("rate,period", [(3, 0), (2, 0), (3, 1)])
+@pytest.mark.parametrize("rate,period", [(3, 0), (2, 0), (3, 1), (4, 0), (5, 0)])
 def test_generic_kernel_nshifts(capi, ctx, oracle, no_hooks, rate, period):
-    """QPSK 3/4 (two symbols per FEC block) and QPSK 4/6 (three): the table-driven kernel, alignments that differ by a symbol shift."""
+    """QPSK 3/4 (two symbols per FEC block), 4/6 (three), 5/6 (three) and 7/8 (four): the table-driven kernel, alignments that differ by a
+    symbol shift."""
     syms = []
     for seed in (4, 11):
         rng = np.random.default_rng(seed)
