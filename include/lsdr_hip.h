@@ -1039,6 +1039,94 @@ void lsdr_rate_est_destroy(lsdr_rate_est *e);
 int lsdr_rate_est_run_async(lsdr_rate_est *e, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
 int lsdr_rate_est_wait(lsdr_rate_est *e, lsdr_rate_estimate *out /* [B] */);
 
+/* ------------------------------------------------------------ the carriers of a wideband capture, found in its spectrum
+ * The step in front of every object above: those take one carrier per capture, and in a recording of a whole transponder the strongest
+ * carrier's lines win and the others are never seen.  The scan reads the averaged power spectrum the way a person reads
+ * lsdr_spectrum_batch's picture: which carriers there are, where, and roughly how wide.  Behind it lsdr_resample_batch takes the same
+ * pointer once per carrier with the centres as tunes, and lsdr_rate_est / lsdr_tune_est refine what the scan read on the decimated
+ * streams.  The reference has no block for this (leansdrscan tries command lines).  It touches no other object's kernels.
+ *
+ * THE DEFINITION, for one capture of n items, N = 4096:
+ *   1 M = min(blocks, n / N) whole blocks.  spread = 0: block b is the capture's b-th.  spread = 1: block b starts at sample b·stride·N,
+ *     stride = max(1, (n / N) / blocks) in integer division — the scan sees the whole recording, not its start;
+ *   2 per block: the samples converted as the capture batch's loads do, float(item − Z)·in_scale; the Hann window from the transform's
+ *     own table, w[n] = 0.5f − 0.5f·(float)cos(2πn/N), z·w component-wise (no division by the RMS: powers stay absolute);
+ *     X = FFT_N (lsdr_tune_est's transform); |X[k]|² of all N bins;
+ *   3 P[k] = Σ_blocks |X[k]|², float, in block order (lsdr_carrier_scan_spectrum_dev, FFT order: bin k is frequency k/N, above N/2 negative);
+ *   4 S[k] = (Σ_{j=−smooth…+smooth} P[(k+j) mod N]) / (float)(2·smooth + 1), float, j ascending: a circular boxcar;
+ *   5 floor = the value of rank N/8 (from 0: the 513th smallest) among the N values of S; T = floor·factor, one float multiply,
+ *     factor = (float)pow(10.0, threshold_db/10.0);
+ *   6 above[k] = S[k] ≥ T.  A run starts at s where above[s] and not above[(s−1) mod N] and lasts while above holds, across the N−1 → 0
+ *     seam if it has to.  Runs are taken in ascending (s + N/2) mod N: by start frequency from −1/2 upward, a run across ±1/2 last.
+ *     All bins above: saturated = 1 and no carriers; none above: no carriers.  Runs of fewer than min_bins bins are dropped; found
+ *     counts the rest, the first max_carriers of them are listed;
+ *   7 per listed run [a, b] (unwrapped indices, S indexed mod N), n = b − a + 1, q = n / 4, in double on the float values of S:
+ *     plateau = (Σ_{k=a+q…b−q} S[k]) / (n − 2q), ascending; L = plateau − floor; H = floor + L/2, the half-power level — a raised-cosine
+ *     spectrum crosses it at ±Fm/2 whatever the roll-off, so the width measured there is the symbol rate.  H < T: weak = 1, lo = a − 0.5,
+ *     hi = b + 0.5.  Otherwise i = the first k ≥ a with S[k] ≥ H, lo = i − (S[i] − H)/(S[i] − S[i−1]); j = the last k ≤ b with S[k] ≥ H,
+ *     hi = j + (S[j] − H)/(S[j] − S[j+1]).  c = (lo + hi)/(2N), center = c − floor(c + 0.5): cycles per sample in [−1/2, 1/2), the sign of
+ *     lsdr_capture_each.tune and of lsdr_spectrum_batch's centre.  bandwidth = (hi − lo)/N, omega = 1/bandwidth, level = L/floor (linear;
+ *     10·log10 of it is the carrier's C/N in dB where the floor is the noise).  Every float is the one nearest to the double value;
+ *   8 a capture with M = 0 gives records (and a spectrum) of all zeros; the unlisted carrier records of a capture are all zeros.
+ * LIMITS.  The floor is a rank statistic of the smoothed spectrum: a front end whose passband droops at the edges, or a band that is more
+ * than 7/8 occupied, biases it.  bandwidth is the symbol rate only for RRC-shaped carriers.  An unmodulated or narrow interferer is listed
+ * like any carrier: `bins` near min_bins, and a later lsdr_rate_est quality below 10, tell it apart.  A weak carrier near the threshold
+ * may come out in pieces.  The picture is of the blocks scanned, not of what happens between them.
+ * ACCURACY, measured on sums of synthetic DVB-S carriers plus noise (tests/scan_common.py, tests/test_carrier_scan_abi.py; DESIGN.md
+ * §4.15) with 64 blocks (16 in brackets): every carrier found and none in noise alone; |omega/true − 1| ≤ 1.7 % (3.4 %) — the boxcar and the
+ * window widen every carrier by about 1 % —; level within 0.2 dB (0.4) of the carriers' C/N; |center − true| ≤ 1.5e-4 cycles per sample
+ * (2.9e-4) for carriers of 8 … 24 samples per symbol 9 … 22 dB above the noise, and 3.7e-4, 1.5 bins (4.6e-4), for one of 4 samples per symbol
+ * at 11.5 dB.  The half-power edges of a carrier 1024 bins wide with 358-bin skirts move with the ±4 % that 64 blocks and 17 bins leave on S:
+ * over twelve other draws of the noise that carrier's centre had a standard deviation of 4.3e-4, up to 7.4e-4 off.  The centre is a coarse
+ * value in any case: lsdr_tune_est on the decimated stream has the fine one.
+ * A capture's records are a pure function of its own converted samples: no atomics, every sum in a fixed order, the runs found in
+ * integers — bit for bit the same alone, in any batch and at any place in it, and in every format that converts to the same floats.
+ * run_async queues everything on the context's stream and returns: one launch over all blocks of all captures, one over the captures,
+ * the records' copies to pinned memory.  wait is one event synchronisation and the read of the records.  One run in flight per object.
+ * iq_dev: as lsdr_rate_est_run_async's.  Nothing behind a capture's last used block is read.
+ * LSDR_E_ARG, with a message naming carrier_scan, the object (if any) left usable: n_captures < 1 (or above 65535), in_format outside the
+ * five LSDR_IN_*, in_scale negative or not finite, blocks > 256, smooth > 64, threshold_db negative or not finite, max_carriers > 64,
+ * nonzero reserved; a misaligned pointer, samples without a pointer, run_async with a run in flight, wait with none. */
+typedef struct lsdr_carrier_scan lsdr_carrier_scan;
+typedef struct {
+  int n_captures;        /* B */
+  int in_format;         /* LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32 */
+  float in_scale;        /* as lsdr_tune_est_cfg.in_scale: 0 or 1 = none; powers scale with its square, the records' ratios do not */
+  unsigned blocks;       /* blocks of 4096 samples per capture, at most 256; 0 = 64 */
+  int spread;            /* 0: the capture's first blocks; otherwise: blocks spread over the whole capture */
+  unsigned smooth;       /* the boxcar's half width in bins, 1 … 64; 0 = 8 */
+  float threshold_db;    /* the threshold above the floor, > 0; 0 = 3 */
+  unsigned min_bins;     /* the shortest run kept; 0 = 2·smooth + 1 */
+  unsigned max_carriers; /* the records per capture, at most 64; 0 = 32 */
+  int reserved[3];       /* 0 */
+} lsdr_carrier_scan_cfg; /* 48 bytes */
+typedef struct {
+  uint32_t blocks;       /* M: the blocks that were used; 0 = no whole block, everything is zero */
+  uint32_t stride;       /* blocks between two used blocks (1 without spread) */
+  uint32_t found;        /* runs of at least min_bins bins */
+  uint32_t listed;       /* min(found, max_carriers): the records that are filled */
+  uint32_t saturated;    /* 1: every bin is above the threshold (no floor to speak of) */
+  uint32_t reserved;
+  float floor;           /* the value of rank N/8 of S */
+  float threshold;       /* T */
+} lsdr_scan_summary;     /* 32 bytes */
+typedef struct {
+  float center;          /* cycles per sample in [−1/2, 1/2): what lsdr_capture_each.tune takes */
+  float bandwidth;       /* cycles per sample between the half-power edges: Fm/Fs of an RRC-shaped carrier */
+  float omega;           /* 1 / bandwidth: samples per symbol */
+  float level;           /* (plateau − floor) / floor, linear */
+  float plateau;         /* mean of S over the run's middle half */
+  uint32_t first_bin;    /* a, 0 … 4095 */
+  uint32_t bins;         /* n */
+  uint32_t weak;         /* 1: the half-power level is under the threshold; the edges are the run's */
+} lsdr_scan_carrier;     /* 32 bytes */
+int lsdr_carrier_scan_create(lsdr_ctx *ctx, const lsdr_carrier_scan_cfg *cfg, lsdr_carrier_scan **e);
+void lsdr_carrier_scan_destroy(lsdr_carrier_scan *e);
+int lsdr_carrier_scan_run_async(lsdr_carrier_scan *e, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
+int lsdr_carrier_scan_wait(lsdr_carrier_scan *e, lsdr_scan_summary *summaries /* [B] */, lsdr_scan_carrier *carriers /* [B·max_carriers] */);
+/* capture i's P of the last run: 4096 floats on the device, FFT order; valid until the next run_async or destroy (NULL: i out of range) */
+const float *lsdr_carrier_scan_spectrum_dev(lsdr_carrier_scan *e, int i);
+
 /* ------------------------------------------------------------ per-stream code rate, estimated from the hard symbols (QPSK)
  * The last constructor argument of the batch decoders that has to be known per capture: lsdr_capture_batch_cfg.fec, leandvb's mandatory
  * --cr.  A capture decoded at the wrong rate gives nothing back and says nothing about why.  The measurement is the reference's own:

@@ -1,6 +1,8 @@
 """ctypes driver for liblsdr_hip.so (include/lsdr_hip.h).  No CPU fallback."""
 import ctypes as C
+import math
 import os
+import time
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -414,6 +416,40 @@ _sig("lsdr_rate_est_create", C.c_int, [vp, C.POINTER(RateEstCfg), C.POINTER(vp)]
 _sig("lsdr_rate_est_destroy", None, [vp])
 _sig("lsdr_rate_est_run_async", C.c_int, [vp, vp, psz])
 _sig("lsdr_rate_est_wait", C.c_int, [vp, C.POINTER(RateEstimate)])
+
+
+class CarrierScanCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("in_format", C.c_int), ("in_scale", C.c_float), ("blocks", C.c_uint), ("spread", C.c_int),
+                ("smooth", C.c_uint), ("threshold_db", C.c_float), ("min_bins", C.c_uint), ("max_carriers", C.c_uint), ("reserved", C.c_int * 3)]
+
+
+class ScanSummary(C.Structure):
+    """lsdr_scan_summary: what the carrier scan found in one capture."""
+    _fields_ = [("blocks", C.c_uint32), ("stride", C.c_uint32), ("found", C.c_uint32), ("listed", C.c_uint32), ("saturated", C.c_uint32),
+                ("reserved", C.c_uint32), ("floor", C.c_float), ("threshold", C.c_float)]
+
+    def as_dict(self):
+        return dict(blocks=int(self.blocks), stride=int(self.stride), found=int(self.found), listed=int(self.listed),
+                    saturated=int(self.saturated), floor=float(self.floor), threshold=float(self.threshold))
+
+
+class ScanCarrier(C.Structure):
+    """lsdr_scan_carrier: one carrier of a capture."""
+    _fields_ = [("center", C.c_float), ("bandwidth", C.c_float), ("omega", C.c_float), ("level", C.c_float), ("plateau", C.c_float),
+                ("first_bin", C.c_uint32), ("bins", C.c_uint32), ("weak", C.c_uint32)]
+
+    def as_dict(self):
+        level = float(self.level)
+        return dict(center=float(self.center), bandwidth=float(self.bandwidth), omega=float(self.omega), level=level,
+                    cnr_db=10.0 * math.log10(level) if level > 0 else float("-inf"), plateau=float(self.plateau),
+                    first_bin=int(self.first_bin), bins=int(self.bins), weak=int(self.weak))
+
+
+_sig("lsdr_carrier_scan_create", C.c_int, [vp, C.POINTER(CarrierScanCfg), C.POINTER(vp)])
+_sig("lsdr_carrier_scan_destroy", None, [vp])
+_sig("lsdr_carrier_scan_run_async", C.c_int, [vp, vp, psz])
+_sig("lsdr_carrier_scan_wait", C.c_int, [vp, C.POINTER(ScanSummary), C.POINTER(ScanCarrier)])
+_sig("lsdr_carrier_scan_spectrum_dev", vp, [vp, C.c_int])
 
 
 HSYM_PACKED2, HSYM_U8, HSYM_SOFT = 0, 1, 2   # lsdr_fec_est's input formats
@@ -1881,6 +1917,164 @@ class ResampledDecoder:
             for i in range(self.n):
                 info[i]["cnr"], info[i]["cnr_center"] = measured[i]["cnr"], t_dec[i]
         return res, ts, info
+
+
+class CarrierScan:
+    """lsdr_carrier_scan: the carriers of each of n_captures wideband captures, read from the averaged power spectrum (Hann-windowed blocks
+    of 4096 samples, `blocks` of them, spread over the whole capture with spread=True): where they are, how wide, how far above the floor.
+    The centres are what ResampleBatch's tune takes (the same pointer once per carrier), omega what resample_design takes."""
+
+    def __init__(self, ctx, n_captures, in_format=IN_CU8, in_scale=0.0, blocks=64, spread=True, smooth=8, threshold_db=3.0, min_bins=0,
+                 max_carriers=32):
+        self.ctx, self.n, self.h = ctx, int(n_captures), None
+        cfg = CarrierScanCfg()
+        cfg.n_captures, cfg.in_format, cfg.in_scale, cfg.blocks, cfg.spread = self.n, int(in_format), float(in_scale), int(blocks), int(bool(spread))
+        cfg.smooth, cfg.threshold_db, cfg.min_bins, cfg.max_carriers = int(smooth), float(threshold_db), int(min_bins), int(max_carriers)
+        h = vp()
+        check(lib.lsdr_carrier_scan_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.max_carriers = int(max_carriers) or 32
+        self._sum = (ScanSummary * self.n)()
+        self._car = (ScanCarrier * (self.n * self.max_carriers))()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_carrier_scan_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _args(self, ptrs, lengths):
+        n = [int(v) for v in lengths]
+        if len(n) != self.n or len(ptrs) != self.n:
+            raise LsdrError(f"carrier scan: {len(ptrs)} pointers and {len(n)} lengths for {self.n} captures")
+        return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in ptrs]), (c_sz * self.n)(*n)
+
+    def run_async(self, ptrs, lengths):
+        """Queues the scan of every capture's first lengths[i] items; a pointer may be None where the length is 0."""
+        check(lib.lsdr_carrier_scan_run_async(self.h, *self._args(ptrs, lengths)))
+
+    def wait(self):
+        check(lib.lsdr_carrier_scan_wait(self.h, self._sum, self._car))
+        out = []
+        for i, s in enumerate(self._sum):
+            d = s.as_dict()
+            d["carriers"] = [self._car[i * self.max_carriers + j].as_dict() for j in range(d["listed"])]
+            out.append(d)
+        return out
+
+    def scan(self, ptrs, lengths):
+        """One run, synchronously: per capture dict(blocks, stride, found, listed, saturated, floor, threshold, carriers=[dict(center,
+        bandwidth, omega, level, cnr_db, plateau, first_bin, bins, weak)]), the carriers by start frequency from −1/2 upward."""
+        self.run_async(ptrs, lengths)
+        return self.wait()
+
+    def spectrum(self, i):
+        """Capture i's summed power spectrum P of the last run (float32[4096], FFT order)."""
+        ptr = lib.lsdr_carrier_scan_spectrum_dev(self.h, int(i))
+        if not ptr:
+            raise LsdrError("carrier scan: no such capture")
+        out = np.empty(4096, np.float32)
+        check(lib.lsdr_memcpy_d2h(self.ctx.h, _np(out), vp(ptr), out.nbytes))
+        self.ctx.sync()
+        return out
+
+
+def group_carriers(carriers, rtol=0.05):
+    """The carriers of one scan sorted by width: ([(omega, [carrier indices])], [indices of the weak ones]) from CarrierScan's records.
+    Taken in ascending omega, a carrier joins the group whose first member it is within rtol of, and a group's omega is that member's — the
+    caller makes one ResampleBatch (one filter, one decimation) per group.  Weak carriers, whose width is their run's and no symbol rate,
+    come back in their own list."""
+    good = sorted((i for i, c in enumerate(carriers) if not c["weak"] and c["omega"] > 0), key=lambda i: (carriers[i]["omega"], i))
+    weak = [i for i in range(len(carriers)) if i not in set(good)]
+    groups = []
+    for i in good:
+        if groups and carriers[i]["omega"] <= groups[-1][0] * (1.0 + rtol):
+            groups[-1][1].append(i)
+        else:
+            groups.append((carriers[i]["omega"], [i]))
+    return [(om, sorted(g)) for om, g in groups], weak
+
+
+class WidebandDecoder:
+    """One wideband capture holding several QPSK DVB-S carriers, from its raw samples to one TS per carrier, out of existing objects:
+    CarrierScan finds the carriers; group_carriers sorts them by width; per group one ResampleBatch takes the same pointer once per carrier
+    with the centres as tunes (resample_design's filter and decimation for the group's omega — also at decimation 1: the other carriers
+    have to be filtered away); RateEstimator(IN_CF32) reads every decimated stream's symbol rate inside ±10 % of the scan's;
+    group_by_omega sorts them again; per subgroup TuneEstimator(IN_CF32) and CaptureBatch(in_format=IN_CF32, in_scale=1) at the estimated
+    omega decode them.  The objects are made per call and closed; every launch is shared by a group's carriers."""
+
+    def __init__(self, ctx, max_samples, in_format=IN_CU8, in_scale=0.0, fec=FEC12, viterbi=None, max_carriers=8, **scan_kw):
+        self.ctx, self.max_samples, self.in_format, self.in_scale = ctx, int(max_samples), in_format, in_scale
+        self.fec, self.viterbi, self.max_carriers, self.scan_kw = fec, viterbi, int(max_carriers), scan_kw
+        self.steps = {}
+
+    def _timed(self, step, t0):
+        self.steps[step] = self.steps.get(step, 0.0) + time.perf_counter() - t0
+
+    def decode(self, ptr, n, min_quality=TUNE_MIN_QUALITY):
+        """(scan, [dict(center, omega_scan, decim, omega, tune, result, ts)]): CarrierScan's record of the capture, and one entry per listed
+        carrier in the scan's order.  A carrier that was not decoded (weak, or no symbol-rate line worth believing on its stream) has
+        decim, omega, tune and result None and an empty ts.  self.steps holds the seconds of the last call's steps (each ends in a wait)."""
+        ctx, n = self.ctx, int(n)
+        if n > self.max_samples:
+            raise LsdrError(f"wideband decoder: {n} samples exceed max_samples {self.max_samples}")
+        self.steps = {}
+        t0 = time.perf_counter()
+        with CarrierScan(ctx, 1, self.in_format, self.in_scale, max_carriers=self.max_carriers, **self.scan_kw) as sc:
+            scan = sc.scan([ptr], [n])[0]
+        self._timed("scan", t0)
+        cars = scan["carriers"]
+        out = [dict(center=c["center"], omega_scan=c["omega"], decim=None, omega=None, tune=None, result=None, ts=b"") for c in cars]
+        groups, _ = group_carriers(cars)
+        for omega_g, members in groups:
+            G = len(members)
+            decim, coeffs = resample_design(omega_g)
+            cap_out = max(1, (n - len(coeffs)) // decim)
+            parts, outs = [], []
+            try:
+                t0 = time.perf_counter()
+                outs = [ctx.alloc(cap_out * 8) for _ in members]
+                optr = [b.ptr for b in outs]
+                rs_ = ResampleBatch(ctx, G, n, coeffs, decim, self.in_format, self.in_scale)
+                parts.append(rs_)
+                centres = [min(max(cars[i]["center"], -0.49998), 0.49998) for i in members]
+                rs = rs_.run([ptr] * G, [n] * G, centres, optr, cap_out)
+                produced = [r["produced"] for r in rs]
+                self._timed("resample", t0)
+                t0 = time.perf_counter()
+                rate = RateEstimator(ctx, G, IN_CF32, 1.0, omega_min=max(0.9 * omega_g / decim, 1.016), omega_max=min(1.1 * omega_g / decim, 64.0))
+                parts.append(rate)
+                rates = rate.estimate(optr, produced)
+                self._timed("rate", t0)
+                for omega, sub in group_by_omega(rates)[0]:
+                    S = len(sub)
+                    sptr, sprod = [optr[k] for k in sub], [produced[k] for k in sub]
+                    t0 = time.perf_counter()
+                    fine = TuneEstimator(ctx, S, IN_CF32, 1.0)
+                    parts.append(fine)
+                    est = fine.estimate(sptr, sprod)
+                    tunes = [e["tune"] if e["quality"] >= min_quality else (centres[k] - rs[k]["applied"]) * decim for e, k in zip(est, sub)]
+                    self._timed("tune", t0)
+                    t0 = time.perf_counter()
+                    warm = -(-int(896 * omega) // 128) * 128              # ResampledDecoder's rule: 896 symbols of warm-up, tiles eight times that
+                    batch = CaptureBatch(ctx, S, cap_out, omega, fec=self.fec, anf=0, viterbi=self.viterbi, in_format=IN_CF32, in_scale=1.0,
+                                         tile_warmup=warm, tile_len=-(-8 * warm // 2048) * 2048)
+                    parts.append(batch)
+                    res, ts = batch.decode_each(sptr, sprod, tunes)
+                    self._timed("decode", t0)
+                    for j, k in enumerate(sub):
+                        out[members[k]].update(decim=decim, omega=omega, tune=tunes[j], result=res[j], ts=ts[j])
+            finally:
+                for p in reversed(parts):
+                    p.close()
+                for b in outs:
+                    b.free()
+        return scan, out
 
 
 def hs2_pack(symbols, offset=0):

@@ -1,4 +1,5 @@
-// leansdr_amd/csrc/block_spectrum.h — what the estimators on raw captures share (lsdr_tune_est: tune_est.hip, lsdr_rate_est: rate_est.hip):
+// leansdr_amd/csrc/block_spectrum.h — what the estimators on raw captures share (lsdr_tune_est: tune_est.hip, lsdr_rate_est: rate_est.hip,
+// lsdr_carrier_scan: carrier_scan.hip):
 // a capture is cut into whole blocks of 4096 samples, one workgroup of 256 turns a block into LDS, applies its own point-wise step, takes the
 // 4096-point FFT and writes |X|² as a row of scratch; a second kernel, one workgroup per capture, sums the rows and finds the first maximum.
 // An estimator adds its point-wise step, its row layout and its record; the samples' conversion is capture_input.h's.
@@ -42,7 +43,7 @@ IN_HD unsigned bs_digit_reverse(unsigned k) {
 }
 
 // ---- the kernels' shared steps (a workgroup of 256) -------------------------------------------------------------------------------------
-struct bs_cap { const unsigned char *in; unsigned blocks, pad; };          // one capture of a run: its samples, its whole blocks (at most the object's)
+struct bs_cap { const unsigned char *in; unsigned blocks, pad; };          // one capture of a run: its samples, its whole blocks (at most the object's); pad: 0, or begin's spread
 
 // Block `block` of the capture at `in`, converted, into x[4096]: one 16-byte piece per thread and pass (item-wise where the capture's pointer
 // is only item-aligned: the same values).  The alignment is decided once, in front of the loop, and the loop stays rolled: the registers of
@@ -145,8 +146,10 @@ struct bs_host {
     return LSDR_OK;
   }
   // The arguments checked (a refused call leaves the object as it was), every capture's record filled and uploaded.  *longest: the most
-  // blocks of any capture; the block kernel's grid is sized for it, and a shorter capture's workgroups leave at once.
-  int begin(lsdr_ctx *c, const char *who, const char *wait_name, const void *const *iq_dev, const size_t *n_samples, unsigned item_bytes, unsigned *longest) {
+  // blocks of any capture; the block kernel's grid is sized for it, and a shorter capture's workgroups leave at once.  spread (the carrier
+  // scan's): the record's pad carries max(1, (n / 4096) / blocks), the distance in blocks between two blocks of a scan over the whole capture.
+  int begin(lsdr_ctx *c, const char *who, const char *wait_name, const void *const *iq_dev, const size_t *n_samples, unsigned item_bytes, unsigned *longest,
+            bool spread = false) {
     const unsigned B = (unsigned)run.n;
     LSDR_TRY(lsdr_in_check_each(who, "tune", B, iq_dev, nullptr, n_samples, nullptr, ~(size_t)0, item_bytes));   // (any length: whole blocks of its front are read)
     LSDR_TRY(run.idle(who, wait_name));
@@ -157,7 +160,7 @@ struct bs_host {
       bs_cap &cap = run.h_caps[i];
       cap.in = reinterpret_cast<const unsigned char *>(iq_dev[i]);
       cap.blocks = whole < blocks ? (unsigned)whole : blocks;
-      cap.pad = 0;
+      cap.pad = spread ? (unsigned)(whole / blocks > 1 ? whole / blocks : 1) : 0;
       if (cap.blocks > *longest) *longest = cap.blocks;
     }
     return run.upload(c->stream);

@@ -1,6 +1,6 @@
 // leansdr_amd/csrc/capture_input.h — the one place that knows the raw captures' sample formats (LSDR_IN_*, include/lsdr_hip.h), for every
 // object that reads captures on the device: lsdr_capture_batch / lsdr_hs_batch (host side only: rxb_host.h, hsb_host.h, capture_batch.hip),
-// lsdr_tune_est, lsdr_rate_est, lsdr_resample_batch, lsdr_spectrum_batch (host side and kernels).  Plain C++ on values, callable from a kernel and from
+// lsdr_tune_est, lsdr_rate_est, lsdr_carrier_scan, lsdr_resample_batch, lsdr_spectrum_batch (host side and kernels).  Plain C++ on values, callable from a kernel and from
 // the host:
 //   the kinds, in_item / in_load / in_unpack / in_piece   an item converted: value = float(item − Z)·in_scale, one rounding per component
 //   lsdr_in_describe, lsdr_in_check_each                   an object's format and scale at create, a run's per-capture arguments
