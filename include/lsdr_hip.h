@@ -780,6 +780,43 @@ int lsdr_capture_batch_notched(lsdr_capture_batch *b, int i, lsdr_cf32 *out_dev,
 /* HIP events around the tile kernel of every run while enabled: mean duration since the previous call, then sets the switch */
 int lsdr_capture_batch_tile_time(lsdr_capture_batch *b, int enable, float *avg_ms, unsigned *launches);
 
+/* Re-acquisition after a lost lock (default engine).  Without it the tail walks the UNLOCKED phase in unlocked_window-byte calls of
+ * deconvol_sync, mpeg_sync behind every one of them, and at the first lock deconvolves everything that is left in one call.  If the lock
+ * drops inside that call — a fade, a burst — mpeg_sync searches the rest alone: the next_sync() it asks for (dvb.h:775-779) finds every
+ * symbol deconvolved already (deconvol_sync::next_sync takes effect on the symbols run() has not read, dvb.h:185-193, 419-470), and a
+ * capture whose carrier loop comes back on a rotation that needs another alignment loses everything behind the burst.  In the reference
+ * the deconvolver is never more than one byte pipe ahead of mpeg_sync, so the request still reaches it.
+ *
+ * relocks = R > 0 keeps that schedule for the whole capture.  Capture i's tail output — the deconvolved bytes up to bytes_deconv, the mpeg
+ * bytes, the RS counts, next_sync_calls, locked, alignment, bitphase, first_lock_byte and the TS — is what this loop makes of the
+ * capture's packed decisions:
+ *   1. deconvol_sync::run with at most unlocked_window bytes of room, at the alignment in force (its own sizes, dvb.h:419-470);
+ *   2. mpeg_sync::run() until nothing moves (dvb.h:743-754);
+ *   3. every next_sync() it asks for;
+ *   4. again, until the deconvolver produces nothing;
+ * with one exception: from the (R+1)-th lock on, a call made while mpeg_sync is locked has the whole remainder for room — the schedule
+ * without re-acquisition, which R = 0 is exactly.  A capture whose lock drops behind such a call is `exhausted`: it ends like a capture
+ * does today.  The locked stretches are still deconvolved and realigned by the whole chip, a stretch of whole windows per launch; that
+ * changes no byte.  The device runs R + 1 such stretches at most, in a fixed sequence of launches with no host read in between; a
+ * capture that needs fewer leaves the others at once.
+ * Limits: R re-acquisitions per capture (at most 16); a search that does not finish before the capture ends gains nothing (mpeg_sync
+ * tries 8 bit phases of 8 packets three times per alignment: up to 4·3·64 packets per round of the four alignments); the default engine
+ * only — in the Viterbi and --hs graphs the alignment search sits in front of the tail.
+ * lsdr_capture_relock_set: for the batches queued after it, every entry point and sample format.  LSDR_E_ARG: relocks > 16, a batch
+ * in flight.  LSDR_E_UNSUPPORTED: a Viterbi object.
+ * lsdr_capture_relock_get: capture i of the waited-for batch.  LSDR_E_ARG: i out of range, no batch waited for.
+ * LSDR_E_UNSUPPORTED: a Viterbi object.  A batch that ran with relocks = 0 leaves the record zero, both byte offsets ~0. */
+typedef struct {
+  uint32_t locks, drops;          /* mpeg_sync: times it locked, times it lost the lock */
+  uint32_t passes;                /* whole-chip stretches this capture used */
+  uint32_t exhausted;             /* 1: the lock dropped behind a call that had the whole remainder for room */
+  uint64_t first_drop_byte;       /* deconvolved-stream offset behind the packet at which the lock first dropped (~0: never) */
+  uint64_t last_lock_byte;        /* … at which mpeg_sync locked last (~0: never), as first_lock_byte counts */
+  uint32_t next_sync_behind_first_lock, pad;   /* next_sync() calls made after the first lock */
+} lsdr_capture_relock_stats;      /* 40 bytes */
+int lsdr_capture_relock_set(lsdr_capture_batch *b, unsigned relocks);   /* 0 = off (default) … 16 */
+int lsdr_capture_relock_get(const lsdr_capture_batch *b, int i, lsdr_capture_relock_stats *s);   /* after wait */
+
 /* Signal reports: per capture what `leandvb --fd-info` prints — cstln_receiver writes FREQ, SS and MER once per meas_decimation samples
  * (sdr.h:857-913: the estimators est_insp / est_sp / est_ep of sdr.h:866-889, freqw behind the drift clamp of sdr.h:895-898; leandvb.cc:428-430,
  * 465, 502, 600-605; leandvb's period is Fs/Finfo).  They tell a weak capture (MER) from a mistuned one (FREQ, held inside

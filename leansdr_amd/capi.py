@@ -328,6 +328,17 @@ _sig("lsdr_capture_any_create", C.c_int, [vp, C.POINTER(CaptureBatchCfg), C.POIN
 _sig("lsdr_capture_any_run_async", C.c_int, [vp, vp, c_sz])
 _sig("lsdr_capture_batch_soft_dev", vp, [vp, C.c_int])
 _sig("lsdr_capture_batch_viterbi_stats", C.c_int, [vp, C.c_int, C.POINTER(CaptureViterbiStats)])
+class CaptureRelockStats(C.Structure):
+    """lsdr_capture_relock_stats: capture i's re-acquisition record (40 bytes)."""
+    _fields_ = [("locks", C.c_uint32), ("drops", C.c_uint32), ("passes", C.c_uint32), ("exhausted", C.c_uint32),
+                ("first_drop_byte", C.c_uint64), ("last_lock_byte", C.c_uint64), ("next_sync_behind_first_lock", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+_sig("lsdr_capture_relock_set", C.c_int, [vp, C.c_uint])
+_sig("lsdr_capture_relock_get", C.c_int, [vp, C.c_int, C.POINTER(CaptureRelockStats)])
 _sig("lsdr_capture_batch_destroy", None, [vp])
 _sig("lsdr_capture_batch_run_async", C.c_int, [vp, vp, c_sz])
 _sig("lsdr_capture_batch_wait", C.c_int, [vp, vp])
@@ -1535,11 +1546,13 @@ class CaptureBatch(_TailBatch):
     in shared launches with the counts on the device.  viterbi=True (or a dict of lsdr_capture_viterbi_cfg fields): the `--viterbi` graph —
     soft symbols, viterbi_sync, mpeg_sync without a deconvolver.  in_format / in_scale (lsdr_capture_input_cfg): captures of IN_CS8,
     IN_CU16, IN_CS16 or IN_CF32 items, converted (and multiplied by in_scale) in the kernels' loads — leandvb's --s8 / --u16 / --s16 /
-    --f32 --float-scale; the converted samples must have an RMS near 75 (the level contract, include/lsdr_hip.h)."""
+    --f32 --float-scale; the converted samples must have an RMS near 75 (the level contract, include/lsdr_hip.h).
+    relock=R (default engine, 0 … 16): re-acquire up to R times after a lost lock — the deconvolver stays one unlocked_window ahead of
+    mpeg_sync until the (R+1)-th lock (lsdr_capture_relock_set); relock_stats(i) after a wait."""
     _c, _what = "lsdr_capture_batch", "capture batch"
 
     def __init__(self, ctx, n_captures, max_samples, omega, fec=FEC12, anf=1, tile_len=0, tile_warmup=0, notch_k=0.0, notch_decimation=0,
-                 unlocked_window=0, aux_cus=0, viterbi=None, in_format=IN_CU8, in_scale=0.0, reports=0):
+                 unlocked_window=0, aux_cus=0, viterbi=None, in_format=IN_CU8, in_scale=0.0, reports=0, relock=0):
         self.ctx, self.n = ctx, int(n_captures)
         cfg = CaptureBatchCfg()
         cfg.n_captures, cfg.max_samples, cfg.omega, cfg.fec, cfg.anf = self.n, int(max_samples), omega, fec, anf
@@ -1563,12 +1576,27 @@ class CaptureBatch(_TailBatch):
         else:
             check(lib.lsdr_capture_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
         self._attach(h, lib.lsdr_capture_any_run_async if self._any else lib.lsdr_capture_batch_run_async, lib.lsdr_capture_each_run_async)
-        if reports:
-            try:
+        self.relock = 0
+        try:
+            if reports:
                 self.set_reports(reports)
-            except Exception:
-                self.close()
-                raise
+            if relock:
+                self.set_relock(relock)
+        except Exception:
+            self.close()
+            raise
+
+    def set_relock(self, relocks):
+        """Re-acquisitions of the batches queued from here on (0: off).  Not while a batch is in flight; not on a Viterbi object."""
+        check(lib.lsdr_capture_relock_set(self.h, int(relocks)))
+        self.relock = int(relocks)
+
+    def relock_stats(self, i):
+        """Capture i's re-acquisition record of the waited-for batch: dict(locks, drops, passes, exhausted, first_drop_byte,
+        last_lock_byte, next_sync_behind_first_lock)."""
+        st = CaptureRelockStats()
+        check(lib.lsdr_capture_relock_get(self.h, int(i), C.byref(st)))
+        return st.as_dict()
 
     def _fec_symbols(self):
         """estimate_fec's input: the soft symbols of a Viterbi object, the packed decisions otherwise."""
@@ -1844,8 +1872,10 @@ class ResampledDecoder:
     rotator): interferers the low-pass removed are not there to be found, and the notch's bins are those of the decimated rate."""
 
     def __init__(self, ctx, n_captures, max_samples, omega, in_format=IN_CU8, in_scale=0.0, fec=FEC12, viterbi=None, anf=0, blocks=8,
-                 rolloff=0.35, rej=10.0, decim=0, cnr_decimation=8 * 4096, **batch_kw):
+                 rolloff=0.35, rej=10.0, decim=0, cnr_decimation=8 * 4096, relock=0, **batch_kw):
         self.ctx, self.n, self.max_samples = ctx, int(n_captures), int(max_samples)
+        if relock and not viterbi:                                       # (the Viterbi engine searches its alignment in front of the tail)
+            batch_kw["relock"] = relock
         self.in_format, self.cnr_decimation, self.measure = in_format, int(cnr_decimation), None
         self.decim, self.coeffs = resample_design(omega, rolloff, rej, decim)
         self.omega_out = float(omega) / self.decim
@@ -2008,8 +2038,9 @@ class WidebandDecoder:
     group_by_omega sorts them again; per subgroup TuneEstimator(IN_CF32) and CaptureBatch(in_format=IN_CF32, in_scale=1) at the estimated
     omega decode them.  The objects are made per call and closed; every launch is shared by a group's carriers."""
 
-    def __init__(self, ctx, max_samples, in_format=IN_CU8, in_scale=0.0, fec=FEC12, viterbi=None, max_carriers=8, **scan_kw):
+    def __init__(self, ctx, max_samples, in_format=IN_CU8, in_scale=0.0, fec=FEC12, viterbi=None, max_carriers=8, relock=0, **scan_kw):
         self.ctx, self.max_samples, self.in_format, self.in_scale = ctx, int(max_samples), in_format, in_scale
+        self.relock = 0 if viterbi else int(relock)                      # CaptureBatch(relock=), default engine only
         self.fec, self.viterbi, self.max_carriers, self.scan_kw = fec, viterbi, int(max_carriers), scan_kw
         self.steps = {}
 
@@ -2063,7 +2094,7 @@ class WidebandDecoder:
                     t0 = time.perf_counter()
                     warm = -(-int(896 * omega) // 128) * 128              # ResampledDecoder's rule: 896 symbols of warm-up, tiles eight times that
                     batch = CaptureBatch(ctx, S, cap_out, omega, fec=self.fec, anf=0, viterbi=self.viterbi, in_format=IN_CF32, in_scale=1.0,
-                                         tile_warmup=warm, tile_len=-(-8 * warm // 2048) * 2048)
+                                         tile_warmup=warm, tile_len=-(-8 * warm // 2048) * 2048, relock=self.relock)
                     parts.append(batch)
                     res, ts = batch.decode_each(sptr, sprod, tunes)
                     self._timed("decode", t0)

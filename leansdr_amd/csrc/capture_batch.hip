@@ -265,6 +265,20 @@ int lsdr_capture_batch_viterbi_stats(const lsdr_capture_batch *b, int i, lsdr_ca
   return LSDR_OK;
 }
 
+// Re-acquisition after a lost lock (include/lsdr_hip.h; tail_relock.h, tail_device.h: k_tail_relock): the tail's own switch
+int lsdr_capture_relock_set(lsdr_capture_batch *b, unsigned relocks) {
+  LSDR_ARG(b);
+  if (b->vb) { lsdr_set_error("capture_batch: re-acquisition belongs to the default engine (a Viterbi object searches the alignment in front of the tail)"); return LSDR_E_UNSUPPORTED; }
+  if (b->in_flight) { lsdr_set_error("capture_batch: a batch is in flight (lsdr_capture_batch_wait first)"); return LSDR_E_ARG; }
+  return lsdr_tail_relock_set(b->tail, relocks);
+}
+int lsdr_capture_relock_get(const lsdr_capture_batch *b, int i, lsdr_capture_relock_stats *s) {
+  LSDR_ARG(b && s);
+  if (b->vb) { lsdr_set_error("capture_batch: re-acquisition belongs to the default engine (a Viterbi object searches the alignment in front of the tail)"); return LSDR_E_UNSUPPORTED; }
+  if (i < 0 || i >= b->cfg.n_captures) { lsdr_set_error("capture_batch: capture %d of %d", i, b->cfg.n_captures); return LSDR_E_ARG; }
+  return lsdr_tail_relock_stats(b->tail, (unsigned)i, s);
+}
+
 int lsdr_capture_batch_bins(lsdr_capture_batch *b, int i, int *bins, unsigned cap, unsigned *n) {
   LSDR_ARG(b && i >= 0 && i < b->cfg.n_captures);
   return lsdr_rxb_bins(b->rx, (unsigned)i, bins, cap, n);

@@ -125,6 +125,8 @@ void lsdr_tail_destroy(lsdr_tail *t);
 int lsdr_tail_bind(lsdr_tail *t, const uint32_t *const *words, const void *counts_dev, size_t count_stride);
 int lsdr_tail_launch(lsdr_tail *t);                                       // … and records "batch done" behind the last kernel
 int lsdr_tail_wait(lsdr_tail *t, lsdr_capture_result *results);           // fills the tail's fields; samples, tiles, seam_* are the owner's
+int lsdr_tail_relock_set(lsdr_tail *t, unsigned relocks);                 // re-acquisitions of the next launches (tail_relock.h); 0: off
+int lsdr_tail_relock_stats(const lsdr_tail *t, unsigned i, lsdr_capture_relock_stats *s);   // after lsdr_tail_wait
 bool lsdr_tail_waited(const lsdr_tail *t);                                // between lsdr_tail_wait and the next launch or lsdr_tail_stale
 void lsdr_tail_stale(lsdr_tail *t);                                       // clears it ahead of a launch that comes later
 int lsdr_tail_ts_download_async(lsdr_tail *t, uint8_t *const *ts_host, size_t cap_bytes);

@@ -18,10 +18,13 @@
 //                     with deconv = NULL (leandvb.cc:530, 563) and its search is a function of the byte stream alone (dvb.h:755-769,
 //                     798-840).  Searches until the lock (or the end), then plans mpeg_sync's locked bulk call like k_tail_acquire;
 //                     k_tail_deconv is not launched, the rest of the tail is the same
+//   k_tail_relock     re-acquisition after a lost lock (off by default): the loop of k_tail_acquire kept up for the whole capture, with the
+//                     locked stretches still deconvolved and realigned by the whole chip (tail_relock.h)
 //   k_tail_deint / k_tail_rs / k_tail_derand_scan / k_tail_derand_apply   the packet kernels, counts read from the record
 #ifndef LSDR_TAIL_DEVICE_H
 #define LSDR_TAIL_DEVICE_H
 
+#include "tail_relock.h"
 
 struct tail_result {             // per capture, host-visible when the batch has run
   unsigned long long n_ts;        // TS packets written
@@ -32,6 +35,9 @@ struct tail_result {             // per capture, host-visible when the batch has
   unsigned next_sync_calls, locked_at_end, alignment, bitphase;
   unsigned long long first_lock_byte;   // deconvolved-stream offset of the first lock (~0: never locked)
 };
+
+// per capture, host-visible when the batch has run: lsdr_capture_relock_stats (include/lsdr_hip.h)
+struct tail_relock_rec { unsigned locks, drops, passes, exhausted; unsigned long long first_drop_byte, last_lock_byte; unsigned next_sync_behind_first_lock, pad; };
 
 struct tail_vit { unsigned long long bytes; unsigned alignment, pad; };   // per capture: what viterbi_sync committed, its current_sync
 
@@ -58,6 +64,11 @@ struct tail_cap {
   long long last_ok;                     // last packet of the bulk with the predicted sync byte (−1: none)
   unsigned long long n_pk, n_ts, rs_errs, first_lock;
   unsigned next_sync_calls, pad;
+  // re-acquisition (k_tail_relock; untouched by the kernels above it)
+  tail_relock_rec *rl;                   // pinned host memory
+  tail_relock_rec rk;                    // the record as it grows
+  unsigned done, fin;                    // nothing is left to do; the last deconvolver call had the whole remainder for room
+  relock_dec saved;                      // the deconvolver's counters in front of the bulk call (its shift register: plan_in0, plan_out0)
 };
 
 struct tail_args {
@@ -387,6 +398,197 @@ __global__ __launch_bounds__(256) void k_tail_book(tail_args A) {
     unsigned long long n = tc.mw >= window ? (tc.mw - window) / kRS + 1 : 0;
     if (n > tc.pk_cap) n = tc.pk_cap;
     tc.n_pk = n;
+  }
+}
+
+// Re-acquisition (lsdr_capture_relock_set, R > 0): the loop of k_tail_acquire, never left.  The capture's deconvolver stays at most
+// one `window` ahead of mpeg_sync for the whole capture, so a next_sync() that mpeg_sync asks for after a lost lock still reaches symbols
+// that have not been deconvolved — until the (R+1)-th lock, from which on a locked mpeg_sync gets the whole remainder in one call (the
+// schedule of k_tail_acquire / k_tail_book).  The host queues R + 2 of these STEPS with k_tail_deconv and k_tail_realign between two of
+// them, and reads nothing in between.  A step
+//   · books the whole-chip call in front of it (k_tail_book's arithmetic).  Where the lock dropped inside a stretch of whole windows,
+//     the bytes stand up to the end of the window in which the windowed schedule notices the drop; the deconvolver is put back to that
+//     boundary (tail_relock.h: counters from the state saved in front of the call, shift register by deconv_carry_after over the
+//     truncated plan) and mpeg_sync goes on from the dropped packet — the stale bytes behind are overwritten in place;
+//   · walks on window by window, by this one workgroup: deconvolve, mpeg_sync::run() until nothing moves, every next_sync();
+//   · leaves where mpeg_sync is locked and a whole-chip call is worth planning — the whole windows of the stretch in one call
+//     (relock_whole_windows; the end of the stream stays with the window loop: its calls are sized by what is left), or everything
+//     once the re-acquisitions are used up — or where the deconvolver produces nothing any more (done: later steps leave at once).
+// The last step plans nothing and walks to the end itself; by then there is nothing to plan (call j is planned at lock j or later, and
+// the call of a lock behind the R-th takes everything).  mw only grows; the packet kernels run once, behind the last step.
+__global__ __launch_bounds__(256) void k_tail_relock(tail_args A, unsigned R, int first, int last) {
+  tail_cap &tc = A.caps[blockIdx.y];
+  __shared__ msync_sh M;
+  __shared__ deconv_plan P;
+  __shared__ deconv_dev D;
+  __shared__ unsigned long long s_n, s_used, s_in0, s_out0;
+  __shared__ int s_again, s_mode, s_leave;
+  const int tid = threadIdx.x;
+  const unsigned long long nsym = *tc.nsym;
+  if (tid == 0) {
+    s_leave = 0;
+    D = A.D;
+    if (first) {
+      tc.locked = 0; tc.skip = 0;
+      for (int i = 0; i < 4; ++i) { tc.n_in[i] = 0; tc.n_out[i] = 0; tc.carry[i].in = 0; tc.carry[i].out = 0; }
+      tc.pos = tc.bw = tc.br = tc.mw = 0;
+      tc.n_pk = tc.n_ts = tc.rs_errs = 0; tc.next_sync_calls = 0; tc.first_lock = ~0ull;
+      tc.plan.n_bytes = 0; tc.bulk_P = 0; tc.drop_at = ~0ull; tc.last_ok = -1;
+      tc.done = 0; tc.fin = 0;
+      tc.rk.locks = tc.rk.drops = tc.rk.passes = tc.rk.exhausted = 0; tc.rk.next_sync_behind_first_lock = 0; tc.rk.pad = 0;
+      tc.rk.first_drop_byte = tc.rk.last_lock_byte = ~0ull;
+      M.S = A.ms0;
+    } else if (tc.done) {
+      s_leave = 1;
+    } else {
+      // the whole-chip call in front of this step
+      msync_state S = tc.ms;
+      const unsigned long long Pk = tc.bulk_P;
+      if (Pk) {
+        unsigned long long donep = Pk;
+        if (tc.drop_at < Pk) {                               // the lock drops at packet drop_at (dvb.h:866-871)
+          donep = tc.drop_at + 1;
+          S.synchronized = 0; S.next_sync_count = 0; S.lock_timeleft = 0;
+          ++tc.rk.drops;
+          if (tc.rk.first_drop_byte == ~0ull) tc.rk.first_drop_byte = tc.br + donep * kRS;
+          if (tc.fin) {
+            tc.rk.exhausted = 1;                              // every symbol has been deconvolved: a next_sync() changes nothing any more
+          } else {
+            const unsigned long long keep = relock_drop_windows(tc.drop_at, tc.saved.bw - tc.br, A.window);
+            if (keep * A.window < tc.plan.n_bytes) {          // rewind to the end of window keep − 1 of the stretch
+              const int a = tc.locked;
+              const relock_call c = relock_plan_call(A.D.pp, A.D.pw, nsym, tc.saved, keep * A.window);
+              deconv_plan T = tc.plan;
+              T.n_bytes = c.n; T.refills = c.refills; T.n_out_end = c.n_out_end;
+              for (int s = 0; s < 4; ++s) D.lut[s] = tc.plan_lut[s];
+              tc.carry[a] = deconv_carry_after<true>(D, T, tc.plan_in0, tc.plan_out0);
+              const relock_dec r = relock_after(A.D.pw, tc.saved, c);
+              tc.pos = r.pos; tc.bw = r.bw; tc.n_in[a] = r.n_in; tc.n_out[a] = r.n_out;
+            }
+          }
+        } else if (tc.last_ok >= 0) {
+          S.lock_timeleft = S.lock_timeout - 1 - (unsigned)(Pk - 1 - (unsigned long long)tc.last_ok);
+        } else {
+          S.lock_timeleft -= (unsigned)Pk;
+        }
+        S.locktime += donep;
+        S.phase8 = (int)((S.phase8 + donep) & 7);
+        tc.br += donep * kRS; tc.mw += donep * kRS;
+      }
+      tc.plan.n_bytes = 0; tc.bulk_P = 0; tc.drop_at = ~0ull; tc.last_ok = -1;
+      M.S = S;
+    }
+  }
+  __syncthreads();
+  if (s_leave) {
+    if (last && tid == 0) { *tc.rl = tc.rk; __threadfence_system(); }
+    return;
+  }
+  bool call = first != 0;                                     // (a later step begins with mpeg_sync over what the call in front of it left)
+  while (true) {
+    if (call) {
+      if (tid == 0) {
+        if (tc.skip) {                                        // in.read(skip), dvb.h:420-421
+          unsigned long long p = (unsigned long long)tc.skip;
+          if (p > nsym - tc.pos) p = nsym - tc.pos;
+          tc.pos += p; tc.skip = 0;
+        }
+        const int a = tc.locked;
+        const bool fin = M.S.synchronized && tc.rk.locks > R;
+        tc.fin = fin ? 1u : 0u;
+        unsigned long long cap = tc.byte_cap - tc.bw;
+        if (!fin && cap > A.window) cap = A.window;
+        int mode = 0;
+        const relock_dec here = {tc.pos, tc.bw, tc.n_in[a], tc.n_out[a]};
+        if (!last && M.S.synchronized) {
+          if (fin) mode = 1;
+          else {
+            const unsigned long long K = relock_whole_windows(A.D.pp, A.D.pw, nsym, tc.byte_cap, A.window, here);
+            if (K) { cap = K * A.window; mode = 1; }
+          }
+        }
+        unsigned char lut[4];
+        deconv_plan Q;
+        unsigned long long used = 0;
+        const unsigned long long n = tail_plan_deconv(A, tc, nsym, cap, Q, lut, &used);
+        if (!n) {
+          mode = 2; tc.done = 1;                              // the symbols have run out
+        } else if (mode == 1) {
+          tc.saved = here;
+          tc.plan = Q;
+          for (int s = 0; s < 4; ++s) tc.plan_lut[s] = lut[s];
+          tc.plan_in0 = tc.carry[a].in; tc.plan_out0 = tc.carry[a].out;
+          tail_commit_deconv(A, tc, Q, used);
+          ++tc.rk.passes;
+          // mpeg_sync's locked call over [br, bw): whole packets with one byte of look-ahead, room permitting (dvb.h:842-846)
+          unsigned long long Pk = 0;
+          if (tc.bw - tc.br >= (unsigned long long)kRS + 1) {
+            Pk = (tc.bw - tc.br - 1) / kRS;
+            const unsigned long long room = (tc.byte_cap - tc.mw) / kRS;
+            if (Pk > room) Pk = room;
+          }
+          tc.bulk_P = Pk;
+        } else {
+          P = Q;
+          for (int s = 0; s < 4; ++s) D.lut[s] = lut[s];
+          s_in0 = tc.carry[a].in; s_out0 = tc.carry[a].out;
+          s_n = n; s_used = used;
+        }
+        s_mode = mode;
+      }
+      __syncthreads();
+      if (s_mode) break;
+      {
+        const bool r12 = deconv_r12_ok(D, P);
+        for (unsigned long long g = tid; 4 * g < s_n; g += 256) deconv_group4<true>(D, P, s_in0, s_out0, g, r12);
+      }
+      __syncthreads();
+      if (tid == 0) {
+        tc.carry[tc.locked] = deconv_carry_after<true>(D, P, s_in0, s_out0);
+        tail_commit_deconv(A, tc, P, s_used);
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+    call = true;
+    // mpeg_sync::run() until nothing moves (the scheduler's fixpoint over this window)
+    do {
+      const bool was = M.S.synchronized != 0;
+      __syncthreads();
+      msync_run_body(M, tc.bytes + tc.br, tc.bw - tc.br, tc.mpeg + tc.mw, tc.byte_cap - tc.mw, tid);
+      if (tid == 0) {
+        const bool now = M.S.synchronized != 0;
+        const unsigned long long at = tc.br + M.R.consumed;
+        if (!was && now) {
+          ++tc.rk.locks; tc.rk.last_lock_byte = at;
+          if (tc.first_lock == ~0ull) tc.first_lock = at;
+        }
+        if (was && !now) {
+          ++tc.rk.drops;
+          if (tc.rk.first_drop_byte == ~0ull) tc.rk.first_drop_byte = at;
+          if (tc.fin) tc.rk.exhausted = 1;
+        }
+        if (M.R.call_next_sync) {                             // deconvol_sync::next_sync, dvb.h:185-193
+          ++tc.next_sync_calls;
+          if (tc.first_lock != ~0ull) ++tc.rk.next_sync_behind_first_lock;
+          ++tc.locked;
+          if (tc.locked == 4) { tc.locked = 0; tc.skip = 1; }
+        }
+        tc.br += M.R.consumed; tc.mw += M.R.produced;
+        s_again = (M.R.consumed || M.R.produced) ? 1 : 0;
+      }
+      __syncthreads();
+    } while (s_again);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    tc.ms = M.S;
+    // deinterleaver<u8>::run (dvb.h:926-948): packets while 17·11·12 + 204 bytes are readable
+    const unsigned long long window = 17 * 11 * 12 + kRS;
+    unsigned long long n = tc.mw >= window ? (tc.mw - window) / kRS + 1 : 0;
+    if (n > tc.pk_cap) n = tc.pk_cap;
+    tc.n_pk = n;
+    if (last) { *tc.rl = tc.rk; __threadfence_system(); }
   }
 }
 

@@ -21,6 +21,8 @@ struct lsdr_tail {
   hipEvent_t ev_done, ev_dl;        // behind the last kernel of a launch; behind the last TS download
   hipStream_t dl;                   // TS downloads
   bool dl_pending, waited;          // waited: between lsdr_tail_wait and the next launch — results and TS are stable
+  unsigned relocks, ran_relocks;    // re-acquisitions asked for (0: off); what the last launch ran with
+  tail_relock_rec *h_rl, *h_rl_dev; // pinned, [n]
 };
 
 static int tail_alloc(lsdr_tail *t, void **p, size_t bytes) {
@@ -76,6 +78,9 @@ int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsig
   LSDR_HIP(hipHostMalloc((void **)&t->h_res, n * sizeof(tail_result), hipHostMallocDefault));
   LSDR_HIP(hipHostGetDevicePointer((void **)&t->h_res_dev, t->h_res, 0));
   memset(t->h_res, 0, n * sizeof(tail_result));
+  LSDR_HIP(hipHostMalloc((void **)&t->h_rl, n * sizeof(tail_relock_rec), hipHostMallocDefault));
+  LSDR_HIP(hipHostGetDevicePointer((void **)&t->h_rl_dev, t->h_rl, 0));
+  memset(t->h_rl, 0, n * sizeof(tail_relock_rec));
   for (unsigned i = 0; i < n; ++i) {
     tail_cap &tc = t->caps[i];
     memset(&tc, 0, sizeof(tc));
@@ -89,6 +94,7 @@ int lsdr_tail_create_ex(lsdr_ctx *c, unsigned n, size_t sym_cap, int rate, unsig
     LSDR_TRY(tail_alloc(t, (void **)&tc.pkt_dst, t->pk_cap * sizeof(long long)));
     tc.byte_cap = t->byte_cap; tc.pk_cap = t->pk_cap;
     tc.res = t->h_res_dev + i;
+    tc.rl = t->h_rl_dev + i;
     if (t->nodeconv) tc.vit = t->d_vit + i;
   }
   t->A.caps = t->d_caps;
@@ -102,6 +108,7 @@ void lsdr_tail_destroy(lsdr_tail *t) {
   for (void *p : t->owned) (void)hipFree(p);
   (void)hipFree(t->d_caps);
   if (t->h_res) (void)hipHostFree(t->h_res);
+  if (t->h_rl) (void)hipHostFree(t->h_rl);
   (void)hipFree(t->d_vit);
   if (t->h_vit) (void)hipHostFree(t->h_vit);
   if (t->dec) lsdr_deconv_destroy(t->dec);
@@ -152,14 +159,27 @@ int lsdr_tail_launch(lsdr_tail *t) {
   if (wide < 16) wide = 16;
   wide = (wide + 7) / 8 * 8;
   const dim3 grid(wide, t->n);
-  if (t->nodeconv) {
-    hipLaunchKernelGGL(k_tail_acquire_bytes, one, dim3(256), 0, c->stream, t->A);
+  t->ran_relocks = t->nodeconv ? 0u : t->relocks;
+  if (t->ran_relocks) {
+    // R + 2 steps of the window loop, a whole-chip call between two of them; nothing is read in between (a capture with nothing to do
+    // leaves every kernel at once)
+    const unsigned R = t->ran_relocks;
+    hipLaunchKernelGGL(k_tail_relock, one, dim3(256), 0, c->stream, t->A, R, 1, 0);
+    for (unsigned p = 0; p <= R; ++p) {
+      hipLaunchKernelGGL(k_tail_deconv, grid, dim3(256), 0, c->stream, t->A);
+      hipLaunchKernelGGL(k_tail_realign, grid, dim3(256), 0, c->stream, t->A);
+      hipLaunchKernelGGL(k_tail_relock, one, dim3(256), 0, c->stream, t->A, R, 0, p == R ? 1 : 0);
+    }
   } else {
-    hipLaunchKernelGGL(k_tail_acquire, one, dim3(256), 0, c->stream, t->A);
-    hipLaunchKernelGGL(k_tail_deconv, grid, dim3(256), 0, c->stream, t->A);
+    if (t->nodeconv) {
+      hipLaunchKernelGGL(k_tail_acquire_bytes, one, dim3(256), 0, c->stream, t->A);
+    } else {
+      hipLaunchKernelGGL(k_tail_acquire, one, dim3(256), 0, c->stream, t->A);
+      hipLaunchKernelGGL(k_tail_deconv, grid, dim3(256), 0, c->stream, t->A);
+    }
+    hipLaunchKernelGGL(k_tail_realign, grid, dim3(256), 0, c->stream, t->A);
+    hipLaunchKernelGGL(k_tail_book, one, dim3(256), 0, c->stream, t->A);
   }
-  hipLaunchKernelGGL(k_tail_realign, grid, dim3(256), 0, c->stream, t->A);
-  hipLaunchKernelGGL(k_tail_book, one, dim3(256), 0, c->stream, t->A);
   hipLaunchKernelGGL(k_tail_deint, grid, dim3(256), 0, c->stream, t->A);
   hipLaunchKernelGGL(k_tail_rs, grid, dim3(256), 0, c->stream, t->A);
   hipLaunchKernelGGL(k_tail_derand_scan, one, dim3(1024), 0, c->stream, t->A);
@@ -185,6 +205,24 @@ int lsdr_tail_wait(lsdr_tail *t, lsdr_capture_result *results) {
     r.bytes_deconv = tr.bytes_deconv; r.bytes_mpeg = tr.bytes_mpeg; r.first_lock_byte = tr.first_lock_byte;
     r.next_sync_calls = tr.next_sync_calls; r.locked = tr.locked_at_end; r.alignment = tr.alignment; r.bitphase = tr.bitphase;
   }
+  return LSDR_OK;
+}
+// Re-acquisitions of the NEXT launches (0: off, the tail as it is without this call); the owner refuses the call while a batch is in flight.
+int lsdr_tail_relock_set(lsdr_tail *t, unsigned relocks) {
+  LSDR_ARG(t);
+  if (t->nodeconv) { lsdr_set_error("%s: re-acquisition belongs to the default engine's tail (deconvol_sync)", t->who); return LSDR_E_UNSUPPORTED; }
+  if (relocks > kRelockMax) { lsdr_set_error("%s: relocks is %u, at most %u", t->who, relocks, kRelockMax); return LSDR_E_ARG; }
+  t->relocks = relocks;
+  return LSDR_OK;
+}
+// Capture i's record of the waited-for batch; a batch that ran with re-acquisition off leaves it zero with both offsets ~0.
+int lsdr_tail_relock_stats(const lsdr_tail *t, unsigned i, lsdr_capture_relock_stats *s) {
+  LSDR_ARG(t && s && i < t->n);
+  if (t->nodeconv) { lsdr_set_error("%s: re-acquisition belongs to the default engine's tail (deconvol_sync)", t->who); return LSDR_E_UNSUPPORTED; }
+  if (!t->waited) { lsdr_set_error("%s: relock stats before lsdr_%s_wait", t->who, t->who); return LSDR_E_ARG; }
+  memset(s, 0, sizeof(*s));
+  s->first_drop_byte = s->last_lock_byte = ~0ull;
+  if (t->ran_relocks) memcpy(s, &t->h_rl[i], sizeof(*s));
   return LSDR_OK;
 }
 bool lsdr_tail_waited(const lsdr_tail *t) { return t && t->waited; }
@@ -218,6 +256,10 @@ size_t lsdr_tail_byte_cap(const lsdr_tail *t) { return t ? t->byte_cap : 0; }
 const uint8_t *lsdr_tail_bytes_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].bytes : nullptr; }
 const uint8_t *lsdr_tail_mpeg_dev(const lsdr_tail *t, unsigned i) { return t && i < t->n ? t->caps[i].mpeg : nullptr; }
 
+static_assert(sizeof(lsdr_capture_relock_stats) == 40 && sizeof(tail_relock_rec) == 40 &&
+              offsetof(lsdr_capture_relock_stats, first_drop_byte) == offsetof(tail_relock_rec, first_drop_byte) &&
+              offsetof(lsdr_capture_relock_stats, next_sync_behind_first_lock) == offsetof(tail_relock_rec, next_sync_behind_first_lock),
+              "include/lsdr_hip.h's lsdr_capture_relock_stats mirrors tail_device.h's tail_relock_rec");
 static_assert(sizeof(lsdr_tail_vit) == sizeof(tail_vit) && offsetof(lsdr_tail_vit, alignment) == offsetof(tail_vit, alignment),
               "lsdr_internal.h mirrors tail_device.h's tail_vit");
 
