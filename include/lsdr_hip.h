@@ -1496,6 +1496,52 @@ int  lsdr_tx_batch_set_noise_margin(lsdr_tx_batch*, float sigmas);         /* a 
 int  lsdr_tx_batch_plan(const lsdr_tx_batch_cfg*, const lsdr_tx_each*, lsdr_tx_result*);   /* host only */
 float lsdr_db_to_amplitude(double db);                                     /* expf(logf(10)*db/20): how both apps parse --power and --awgn */
 
+/* ------------------------------------------------------------ TS stitch: the streams of a recording's overlapping pieces, joined
+ * A recording longer than a batch decoder's max_samples is decoded in pieces that overlap; every piece acquires anew at its start, so
+ * adjacent pieces' transport streams share a stretch of packets.  This object takes P transport streams in device memory, in recording
+ * order — the batch decoders' *_ts_dev(i) or any uploaded TS, each with its own length; a length of 0 with a NULL pointer is valid —
+ * finds where each continues the one before it and writes them, every packet once, into one device buffer.  It reads TS buffers and
+ * touches no decode kernel.
+ *
+ * THE DEFINITION.  All integers: every implementation agrees bit for bit (tests/stitch_common.py restates it in numpy).
+ *   the join of the pair (k, k+1).  T is the last min(W, n_k) packets of stream k, H the first min(W, n_k+1) packets of stream k+1.  A RUN
+ *            is a maximal stretch of L consecutive pairs T[b+i], H[a+i] (i = 0 … L−1) whose 188 bytes are equal.  Equality is by bytes:
+ *            the kernels pre-filter with a 64-bit key, a byte compare decides, a key collision can never join.  A run QUALIFIES if L ≥ M
+ *            and at least ⌈M/2⌉ of its packets are not null packets (PID 0x1fff, (b[1]&0x1f)<<8 | b[2]).  The join is the longest
+ *            qualifying run, ties to the smallest a, then the smallest b:
+ *              joined = 1, run = L, end = (n_k − |T|) + b + L  (stream k is kept up to here), next_start = a + L  (stream k+1 from here).
+ *            Without a qualifying run: joined = 0, run = 0, end = n_k, next_start = 0 — nothing is dropped and the caller is told.
+ *   the kept range of stream k is [start, max(start, end)) with start = the join (k−1, k)'s next_start (0 for k = 0) and end = the join
+ *            (k, k+1)'s end (n_k for k = P−1): a stream shorter than both of its overlaps keeps nothing.
+ *   the output is the kept ranges one behind the other, stream 0 first: keep[k] = {start, end, out_offset}, out_offset in packets.
+ * The join of a pair depends on the two streams alone: the same records alone, at any position of a larger batch and on a reused object.
+ * QUEUEING.  run_async queues five launches on the context's stream — their number does not depend on P — and the records' copy, and
+ * returns; the host reads nothing before wait, which is one synchronisation and the read of pinned records.  One run in flight per
+ * object.  download_async (after wait) copies the output on a stream of its own and may still be pending when the next run_async is
+ * queued: the kernel that writes the output waits for it.
+ * The kernels read the 16-byte lines that hold a stream's first and last byte whole (a line never leaves the page its bytes are in).
+ * LSDR_E_ARG, with a message naming ts_stitch, the object (if any) left usable: n_streams outside 1 … 65535, window above 65535, min_run
+ * above the window, nonzero reserved, n_packets[i] > max_packets, a NULL or not 4-byte aligned pointer with packets, run_async with a run
+ * in flight, wait with none, a download before a wait or into too small a buffer.  LSDR_E_UNSUPPORTED: max_packets ≥ 2^32. */
+typedef struct lsdr_ts_stitch lsdr_ts_stitch;
+typedef struct {
+  int n_streams;
+  size_t max_packets;        /* per stream; the output buffer holds n_streams × max_packets packets */
+  unsigned window;           /* W; 0: 4096 */
+  unsigned min_run;          /* M; 0: 8 */
+  int reserved[8];           /* 0 */
+} lsdr_ts_stitch_cfg;
+typedef struct { uint32_t joined, run; uint64_t end, next_start; } lsdr_ts_join;   /* 24 bytes */
+typedef struct { uint64_t start, end, out_offset; } lsdr_ts_keep;                  /* 24 bytes */
+int  lsdr_ts_stitch_create(lsdr_ctx*, const lsdr_ts_stitch_cfg*, lsdr_ts_stitch**);
+void lsdr_ts_stitch_destroy(lsdr_ts_stitch*);
+/* ts_dev: HOST array of n_streams DEVICE pointers, 4-byte aligned (may be NULL where n_packets is 0); n_packets: HOST */
+int  lsdr_ts_stitch_run_async(lsdr_ts_stitch*, const uint8_t *const *ts_dev, const uint64_t *n_packets);
+int  lsdr_ts_stitch_wait(lsdr_ts_stitch*, lsdr_ts_join *joins /* [n_streams − 1], may be NULL */, lsdr_ts_keep *keep /* [n_streams], may be NULL */);
+const uint8_t *lsdr_ts_stitch_out_dev(const lsdr_ts_stitch*);             /* (keep[P−1].out_offset + its length) × 188 bytes after wait */
+int  lsdr_ts_stitch_download_async(lsdr_ts_stitch*, uint8_t *host, size_t cap_bytes);
+int  lsdr_ts_stitch_download_wait(lsdr_ts_stitch*);
+
 #ifdef __cplusplus
 }
 #endif

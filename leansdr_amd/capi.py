@@ -575,6 +575,35 @@ _sig("lsdr_ts_batch_download_wait", C.c_int, [vp])
 _sig("lsdr_ts_batch_tile", C.c_uint, [vp])
 
 
+class TsStitchCfg(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("max_packets", C.c_size_t), ("window", C.c_uint), ("min_run", C.c_uint), ("reserved", C.c_int * 8)]
+
+
+class TsJoin(C.Structure):
+    """lsdr_ts_join: where stream k + 1 continues stream k (24 bytes)."""
+    _fields_ = [("joined", C.c_uint32), ("run", C.c_uint32), ("end", C.c_uint64), ("next_start", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class TsKeep(C.Structure):
+    """lsdr_ts_keep: the packets [start, end) a stitch keeps of a stream, and their place in the output (24 bytes)."""
+    _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("out_offset", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+_sig("lsdr_ts_stitch_create", C.c_int, [vp, C.POINTER(TsStitchCfg), C.POINTER(vp)])
+_sig("lsdr_ts_stitch_destroy", None, [vp])
+_sig("lsdr_ts_stitch_run_async", C.c_int, [vp, vp, C.POINTER(C.c_uint64)])
+_sig("lsdr_ts_stitch_wait", C.c_int, [vp, C.POINTER(TsJoin), C.POINTER(TsKeep)])
+_sig("lsdr_ts_stitch_out_dev", vp, [vp])
+_sig("lsdr_ts_stitch_download_async", C.c_int, [vp, vp, c_sz])
+_sig("lsdr_ts_stitch_download_wait", C.c_int, [vp])
+
+
 class TxBatchCfg(C.Structure):
     """lsdr_tx_batch_cfg"""
     _fields_ = [("n_streams", C.c_int), ("max_packets", C.c_size_t), ("cstln", C.c_int), ("interp", C.c_int), ("decim", C.c_int),
@@ -1383,6 +1412,105 @@ class TsBatch:
         return res, [b[:s["kept"] * 188].tobytes() for b, s in zip(bufs, res)], idx
 
 
+class TsStitch:
+    """lsdr_ts_stitch: n_streams transport streams in device memory, in recording order, each continuing the one before it somewhere
+    inside an overlap, joined into one with every packet once (include/lsdr_hip.h has the definition: the join of a pair is the longest
+    run of at least min_run byte-equal packets, enough of them not null, between the last `window` packets of one stream and the first
+    `window` of the next)."""
+
+    def __init__(self, ctx, n_streams, max_packets, window=4096, min_run=8):
+        self.ctx, self.n, self.h = ctx, int(n_streams), None
+        cfg = TsStitchCfg()
+        cfg.n_streams, cfg.max_packets, cfg.window, cfg.min_run = self.n, int(max_packets), int(window), int(min_run)
+        h = vp()
+        check(lib.lsdr_ts_stitch_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.max_packets, self.window, self.min_run = int(max_packets), int(window) or 4096, int(min_run) or 8
+        self._joins, self._keep = (TsJoin * max(self.n - 1, 1))(), (TsKeep * self.n)()
+        self.packets = 0
+
+    def close(self):
+        if self.h:
+            lib.lsdr_ts_stitch_destroy(self.h)
+            self.h = None
+
+    def run_async(self, ptrs, n_packets):
+        """Queues one run: ptrs device pointers (None where there are no packets), n_packets per stream."""
+        n = [int(v) for v in n_packets]
+        if len(n) != self.n or len(ptrs) != self.n:
+            raise LsdrError(f"ts stitch: {len(ptrs)} pointers and {len(n)} lengths for {self.n} streams")
+        p = (vp * self.n)(*[q if isinstance(q, vp) else vp(q) for q in ptrs])
+        check(lib.lsdr_ts_stitch_run_async(self.h, p, (C.c_uint64 * self.n)(*n)))
+
+    def wait(self):
+        """([dict(joined, run, end, next_start)] per pair, [dict(start, end, out_offset)] per stream); self.packets: the output's."""
+        check(lib.lsdr_ts_stitch_wait(self.h, self._joins, self._keep))
+        keep = [k.as_dict() for k in self._keep]
+        self.packets = keep[-1]["out_offset"] + keep[-1]["end"] - keep[-1]["start"]
+        return [j.as_dict() for j in self._joins[:self.n - 1]], keep
+
+    def out_ptr(self):
+        return lib.lsdr_ts_stitch_out_dev(self.h)
+
+    def download(self):
+        """The output of the run waited for (bytes), over the object's download stream."""
+        a = np.empty(self.packets * 188, np.uint8)
+        check(lib.lsdr_ts_stitch_download_async(self.h, _np(a), a.nbytes))
+        check(lib.lsdr_ts_stitch_download_wait(self.h))
+        return a.tobytes()
+
+    def stitch_records(self, ptrs, n_packets):
+        """One run, synchronously: (joins, keep); the stitched TS stays on the device (out_ptr(), self.packets packets)."""
+        self.run_async(ptrs, n_packets)
+        return self.wait()
+
+    def stitch(self, ptrs, n_packets):
+        """One run, synchronously: (joins, keep, the stitched TS's bytes)."""
+        joins, keep = self.stitch_records(ptrs, n_packets)
+        return joins, keep, self.download()
+
+
+def unjoined(joins):
+    """The indices k of the pairs (k, k + 1) a stitch could not join."""
+    return [k for k, j in enumerate(joins) if not j["joined"]]
+
+
+def recording_plan(n_samples, piece_samples, overlap_samples):
+    """The pieces a recording of n_samples is decoded in, [(first sample, length)], in closed form: piece i starts at i·(piece − overlap),
+    the last may be short, and there are max(1, ⌈(n − overlap) / (piece − overlap)⌉) of them.  Piece and overlap are multiples of 8 samples
+    (overlap_for gives multiples of 4096), so every piece of a 16-byte aligned recording starts 16-byte aligned in every sample format.
+    No GPU, no context."""
+    n, piece, overlap = int(n_samples), int(piece_samples), int(overlap_samples)
+    if piece % 8 or overlap % 8 or not 0 <= overlap < piece:
+        raise LsdrError(f"recording: piece ({piece}) and overlap ({overlap}) must be multiples of 8 samples with 0 <= overlap < piece")
+    stride = piece - overlap
+    count = max(1, -(-(n - overlap) // stride))
+    return [(i * stride, max(0, min(piece, n - i * stride))) for i in range(count)]
+
+
+#: 2500 − the most packets the capture batch returned of the 2500 sent, plus the most it locked behind the reference (`late`), per code
+#: rate: README.md's table "Acquisition, batch against reference" (tests/test_gpu_capture_batch_rates.py, 1.2 samples per symbol)
+ACQUISITION_PACKETS = {FEC12: 2500 - 2443 + 0, FEC23: 2500 - 2426 + 64, FEC34: 2500 - 2458 + 72, FEC56: 2500 - 2425 + 46, FEC78: 2500 - 2473 + 56}
+FEC_RATE = {FEC12: (1, 2), FEC23: (2, 3), FEC34: (3, 4), FEC56: (5, 6), FEC78: (7, 8)}
+
+
+def overlap_for(fec, omega, packets=None, window=4096):
+    """An overlap in samples for RecordingDecoder: `packets` RS packets of 204·8 bits at 2·rate bits per symbol and omega samples per
+    symbol, packets·204·8 / (2·rate)·omega, rounded up to a multiple of 4096.
+    packets None: ACQUISITION_PACKETS[fec] + window.  A piece returns nothing of its first ACQUISITION_PACKETS[fec] packets — the table
+    above is what the README's rate table records: the packets missing from the best of nine 2500-packet captures per rate, which counts
+    the few lost at the capture's end as well, plus the most the batch locked behind the reference there — and behind them the overlap
+    then holds `window` packets, all that a join looks at.  Measured at 1.2 samples per symbol with the default engine only; the table
+    has no entry for other rates, and this function refuses them."""
+    if fec not in ACQUISITION_PACKETS:
+        raise LsdrError(f"overlap_for: no acquisition figure for code rate {fec}")
+    if packets is None:
+        packets = ACQUISITION_PACKETS[fec] + int(window)
+    num, den = FEC_RATE[fec]
+    samples = int(packets) * 204 * 8 * den / (2 * num) * float(omega)
+    return -(-int(math.ceil(samples)) // 4096) * 4096
+
+
 def ts_bitrate(summary):
     """The stream's bit rate from its PCRs: the bits between the first and the last packet that carry one, over the time between the two
     values (27 MHz ticks, the 33-bit base wraps).  None with fewer than two PCRs or no difference."""
@@ -1424,6 +1552,10 @@ class _TailBatch:
         if tsb:
             tsb.close()
             self._ts_batch = None
+        tss = getattr(self, "_ts_stitch", None)
+        if tss:
+            tss.close()
+            self._ts_stitch = None
         if self.h:
             self._fn("destroy")(self.h)
             self.h = None
@@ -1449,6 +1581,17 @@ class _TailBatch:
         keep_pids, drop_null, drop_tei, drop_sync, index."""
         tsb, ptrs, n = self._ts_object(results)
         return tsb.filter(ptrs, n, **rule)
+
+    def ts_stitch(self, results, window=4096, min_run=8):
+        """After a wait, where the batch's captures are the overlapping pieces of one recording in order: TsStitch.stitch over every
+        capture's TS on the device — (joins, keep, the stitched TS's bytes).  The decode is not touched."""
+        n = [int(r["ts_packets"]) for r in results]
+        tss = getattr(self, "_ts_stitch", None)
+        if not tss or tss.max_packets < max(n + [1]) or (tss.window, tss.min_run) != (int(window), int(min_run)):
+            if tss:
+                tss.close()
+            self._ts_stitch = tss = TsStitch(self.ctx, self.n, max(n + [1]), window, min_run)
+        return tss.stitch([self._fn("ts_dev")(self.h, i) if n[i] else None for i in range(self.n)], n)
 
     def estimate_fec(self, results, max_symbols=16384):
         """After a wait: every capture's code rate, estimated from the hard decisions the run left on the device (FecEstimator over the
@@ -1693,6 +1836,206 @@ class HsBatch(_TailBatch):
     def symbols(self, i, n):
         """The first n hard symbols of capture i after a run (host)."""
         return self._fetch(self.symbols_ptr(i), n)
+
+
+IN_ITEM_BYTES = {IN_CU8: 2, IN_CS8: 2, IN_CU16: 4, IN_CS16: 4, IN_CF32: 8}
+
+
+class RecordingDecoder:
+    """A recording of any length from its raw samples to one TS: cut into pieces of piece_samples that overlap by overlap_samples
+    (recording_plan), decoded pieces_per_batch at a time as the captures of one batch (CaptureBatch, in either engine, or HsBatch with
+    hs=True — each piece acquires anew), and the pieces' TS joined on the device (TsStitch, with `window` and `min_run`), the join between
+    the last piece of one batch and the first of the next included.  tune: leandvb's --tune as Ftune/Fs in cycles per sample for every
+    piece; None: estimated once, from the first piece (TuneEstimator; 0 where its quality is below TUNE_MIN_QUALITY).
+    decode / decode_file return (the TS's bytes, report): report = dict(pieces: [dict(first_sample, n_samples, result, keep: [start, end)
+    of the piece's TS, ts: its bytes with piece_ts=True, head_in_front: see below)], joins: [dict(joined, run, end, next_start)] per adjacent pair, unjoined: the
+    indices of the pairs that did not join, tune, packets).  The TS is the stitch's output with one exception: where the left piece of a join is kept
+    from its first packet and holds fewer packets in front of the run than the right piece (it acquired late, behind a fade, beside a
+    neighbour that started in the clear), the right piece's packets in front of the run go out in place of the left piece's: the left
+    piece's record gains head_in_front (the packets taken from its neighbour) and dropped_in_front (its own, left out)."""
+
+    def __init__(self, ctx, piece_samples, overlap_samples, pieces_per_batch, omega, fec=FEC12, viterbi=None, hs=False, in_format=IN_CU8,
+                 in_scale=0.0, relock=0, tune=None, window=4096, min_run=8, piece_ts=False, **batch_kw):
+        self.ctx, self.piece, self.overlap, self.B = ctx, int(piece_samples), int(overlap_samples), int(pieces_per_batch)
+        recording_plan(0, self.piece, self.overlap)                     # (checks the two)
+        if self.B < 1:
+            raise LsdrError("recording: pieces_per_batch must be at least 1")
+        if hs and (in_format != IN_CU8 or in_scale != 0.0 or fec != FEC12 or viterbi or relock):
+            raise LsdrError("recording: hs=True decodes cu8 samples at rate 1/2, without viterbi= and relock=")
+        self.in_format, self.in_scale, self.item = int(in_format), float(in_scale), IN_ITEM_BYTES[int(in_format)]
+        self.tune, self.piece_ts, self.window, self.min_run = tune, bool(piece_ts), int(window), int(min_run)
+        num, den = (1, 2) if hs else FEC_RATE[fec]
+        # a piece's packets: its symbols carry 2·rate bits each, a packet is 204·8 of them; 1 % and 64 packets of room (omega is nominal)
+        self.max_packets = int(1.01 * self.piece / float(omega) * 2 * num / den / 1632) + 64
+        self._parts, self._bufs, self._est = [], [], None
+        try:
+            if hs:
+                self.batch = self._own(HsBatch(ctx, self.B, self.piece, omega, **batch_kw))
+            else:
+                self.batch = self._own(CaptureBatch(ctx, self.B, self.piece, omega, fec=fec, viterbi=viterbi, in_format=in_format,
+                                                    in_scale=in_scale, relock=0 if viterbi else relock, **batch_kw))
+            self._make_stitcher(self.max_packets)
+        except Exception:
+            self.close()
+            raise
+
+    def _own(self, part):
+        self._parts.append(part)
+        return part
+
+    def _make_stitcher(self, max_packets):
+        """The stitcher of a batch's pieces behind slot 0, which holds the last piece of the batch before (self._carry: its TS, copied)."""
+        old = getattr(self, "stitcher", None)
+        self.stitcher = self._own(TsStitch(self.ctx, self.B + 1, max_packets, self.window, self.min_run))
+        carry = self.ctx.alloc(max(max_packets, 1) * 188)
+        if old:
+            check(lib.lsdr_memcpy_d2d(self.ctx.h, carry.ptr, self._carry.ptr, self.max_packets * 188))
+            self.ctx.sync()
+            self._parts.remove(old)
+            old.close()
+            self._carry.free()
+        self._carry, self.max_packets = carry, int(max_packets)
+
+    def close(self):
+        for p in reversed(self._parts):
+            p.close()
+        for b in self._bufs + ([self._carry] if getattr(self, "_carry", None) else []):
+            b.free()
+        for p in getattr(self, "_pinned", []):
+            lib.lsdr_free_host(p)
+        if self._est:
+            self._est.close()
+        self._parts, self._bufs, self._pinned, self._carry, self._est = [], [], [], None, None
+
+    def plan(self, n_samples):
+        """recording_plan with this object's piece and overlap."""
+        return recording_plan(n_samples, self.piece, self.overlap)
+
+    def batch_span(self, pieces):
+        """The samples [first, end) that a batch of consecutive pieces reads."""
+        return pieces[0][0], pieces[-1][0] + pieces[-1][1]
+
+    def _tune_of(self, ptr, n):
+        if self.tune is not None:
+            return float(self.tune)
+        if not self._est:
+            self._est = TuneEstimator(self.ctx, 1, self.in_format, self.in_scale)
+        e = self._est.estimate([ptr], [n])[0]
+        return e["tune"] if e["quality"] >= TUNE_MIN_QUALITY else 0.0
+
+    def _start(self):
+        return dict(pieces=[], joins=[], unjoined=[], tune=None, packets=0), [], None
+
+    def _batch_async(self, base_ptr, first_sample, pieces, tune):
+        """Queues the decode of consecutive pieces; base_ptr holds the recording from first_sample on."""
+        ptrs = [vp(base_ptr + (s - first_sample) * self.item) if n else None for s, n in pieces] + [None] * (self.B - len(pieces))
+        self.batch.run_each_async(ptrs, [n for _, n in pieces] + [0] * (self.B - len(pieces)), tune)
+
+    def _batch_finish(self, pieces, last, report, out, carry):
+        """Waits for the batch, joins its pieces behind the carried one and appends what is final to `out`: everything in front of the
+        batch's last piece, whose own end the next batch's first piece decides (last: there is none).  Returns the new carry,
+        (its packets, the start of its kept range, its index among the pieces)."""
+        res = self.batch.wait()[:len(pieces)]
+        n = [int(r["ts_packets"]) for r in res]
+        if max(n + [0]) > self.max_packets:
+            self._make_stitcher(max(n))
+        ts_dev = self.batch._fn("ts_dev")
+        ptrs = [self._carry.ptr if carry and carry[0] else None] + [ts_dev(self.batch.h, i) if n[i] else None for i in range(len(pieces))]
+        ptrs += [None] * (self.B - len(pieces))
+        joins, keep = self.stitcher.stitch_records(ptrs, [carry[0] if carry else 0] + n + [0] * (self.B - len(pieces)))
+        first = len(report["pieces"])
+        for i, ((s, ns), r) in enumerate(zip(pieces, res)):
+            rec = dict(first_sample=s, n_samples=ns, result=r, keep=[keep[i + 1]["start"], keep[i + 1]["end"]])
+            if self.piece_ts:
+                rec["ts"] = self.batch._fetch(ts_dev(self.batch.h, i), n[i] * 188).tobytes()
+            report["pieces"].append(rec)
+        skip = 0
+        if carry:                                                        # slot 0 is kept from 0 there; its range starts where its own batch said
+            skip = min(carry[1], keep[0]["end"])
+            report["pieces"][carry[2]]["keep"] = [carry[1], max(carry[1], keep[0]["end"])]
+        report["joins"] += joins[0 if carry else 1:len(pieces)]
+        final = self.stitcher.packets if last else keep[len(pieces)]["out_offset"]
+        # A join drops what the right piece holds in front of the run: the left piece holds it too — unless the left piece acquired late
+        # (behind a fade) beside a right neighbour that started in the clear.  Where the left piece is kept from its first packet and has
+        # fewer packets in front of the run than the right piece, the right piece's are the ones that go out there.
+        starts, pos = [carry[1] if carry else 0] + [k["start"] for k in keep[1:]], skip
+        for i in range(0 if carry else 1, len(pieces)):                  # the join of slot i and slot i + 1, which is piece i of the batch
+            j = joins[i]
+            head, mine = j["next_start"] - j["run"], j["end"] - j["run"]
+            if j["joined"] and starts[i] == 0 and head > mine:
+                at = keep[i]["out_offset"]
+                if at > pos:
+                    out.append(self.batch._fetch(vp(self.stitcher.out_ptr() + pos * 188), (at - pos) * 188).tobytes())
+                out.append(self.batch._fetch(ts_dev(self.batch.h, i), head * 188).tobytes())
+                report["pieces"][first + i - 1].update(head_in_front=head, dropped_in_front=mine)
+                pos = at + mine
+        if final > pos:
+            out.append(self.batch._fetch(vp(self.stitcher.out_ptr() + pos * 188), (final - pos) * 188).tobytes())
+        if last:
+            return None
+        k = len(pieces) - 1
+        if n[k]:
+            check(lib.lsdr_memcpy_d2d(self.ctx.h, self._carry.ptr, ts_dev(self.batch.h, k), n[k] * 188))
+        return n[k], keep[k + 1]["start"], first + k
+
+    def _finish(self, report, out, tune):
+        ts = b"".join(out)
+        report["unjoined"], report["tune"], report["packets"] = unjoined(report["joins"]), tune, len(ts) // 188
+        return ts, report
+
+    def decode(self, ptr, n_samples):
+        """A recording of n_samples items resident in device memory at ptr (16-byte aligned): (TS bytes, report)."""
+        ptr = ptr.value if isinstance(ptr, vp) else int(ptr)
+        plan = self.plan(n_samples)
+        report, out, carry = self._start()
+        tune = self._tune_of(vp(ptr), plan[0][1])
+        for g in range(0, len(plan), self.B):
+            pieces = plan[g:g + self.B]
+            self._batch_async(ptr, 0, pieces, tune)
+            carry = self._batch_finish(pieces, g + self.B >= len(plan), report, out, carry)
+        return self._finish(report, out, tune)
+
+    def decode_file(self, path):
+        """A recording in a file of in_format items, streamed through two pinned host buffers and two device buffers of one batch's
+        samples each: while a batch decodes, the next one is read and uploaded on the context's upload stream; consecutive batches share
+        overlap_samples of input.  One host thread.  (TS bytes, report)."""
+        n_samples = os.path.getsize(path) // self.item
+        plan = self.plan(n_samples)
+        groups = [plan[g:g + self.B] for g in range(0, len(plan), self.B)]
+        cap = max((self.B - 1) * (self.piece - self.overlap) + self.piece, 1) * self.item
+        if not self._bufs:
+            self._bufs = [self.ctx.alloc(cap) for _ in range(2)]
+            self._pinned = []
+            for _ in range(2):
+                p = vp()
+                check(lib.lsdr_malloc_host(cap, C.byref(p)))
+                self._pinned.append(p)
+        host = [np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (cap,)) for p in self._pinned]
+        report, out, carry = self._start()
+        with open(path, "rb", buffering=0) as f:
+            def upload(g):
+                first, end = self.batch_span(groups[g])
+                nbytes = (end - first) * self.item
+                f.seek(first * self.item)
+                view, got = memoryview(host[g % 2])[:nbytes], 0
+                while got < nbytes:
+                    k = f.readinto(view[got:])
+                    if not k:
+                        break
+                    got += k
+                if got != nbytes:
+                    raise LsdrError(f"recording: {path}: read {got} of {nbytes} bytes at sample {first}")
+                check(lib.lsdr_copy_h2d_async(self.ctx.h, self._bufs[g % 2].ptr, self._pinned[g % 2], nbytes))
+            upload(0)
+            check(lib.lsdr_copy_fence(self.ctx.h))
+            tune = self._tune_of(vp(self._bufs[0].ptr), plan[0][1])
+            for g, pieces in enumerate(groups):
+                check(lib.lsdr_copy_fence(self.ctx.h))
+                self._batch_async(self._bufs[g % 2].ptr, pieces[0][0], pieces, tune)
+                if g + 1 < len(groups):
+                    upload(g + 1)                                        # (batch g − 1, the last reader of these two buffers, was waited for)
+                carry = self._batch_finish(pieces, g + 1 == len(groups), report, out, carry)
+        return self._finish(report, out, tune)
 
 
 def resample_design(omega, rolloff=0.35, rej=10.0, decim=0):
