@@ -1542,6 +1542,122 @@ const uint8_t *lsdr_ts_stitch_out_dev(const lsdr_ts_stitch*);             /* (ke
 int  lsdr_ts_stitch_download_async(lsdr_ts_stitch*, uint8_t *host, size_t cap_bytes);
 int  lsdr_ts_stitch_download_wait(lsdr_ts_stitch*);
 
+/* ------------------------------------------------------------ a carrier that moves: its track along the capture (QPSK)
+ * The batch decoders hold every tile within ± 1/(2048·omega) cycles per sample of ONE tune per capture (the TUNING CONTRACT), and
+ * lsdr_tune_est reads that one number from the capture's first blocks.  An oscillator that wanders or a pass that sweeps leaves that
+ * window within the capture.  lsdr_tune_track reads the offset ALONG the capture; lsdr_derotate_batch (below) takes a track out of the
+ * samples.  Both run in front of the decoders and touch none of their kernels.
+ *
+ * THE TRACKER.  For one capture of n items, with N = 4096:
+ *   1 FRAMES.  Frame k starts at sample s_k = k·hop, for every k with s_k + blocks·N ≤ n.  If e = ⌊(n − blocks·N)/N⌋·N lies behind the
+ *     last of them, one more frame starts at e: the track then reaches the capture's end.  n < blocks·N: no frame, an all-zero summary.
+ *   2 SPECTRUM of a frame: steps 1 to 4 of lsdr_tune_est on the frame's `blocks` blocks — convert, divide each block by its own RMS,
+ *     w = z⁴, X = FFT_N(w), P[k] = Σ_blocks |X[k]|² in block order.
+ *   3 PEAK.  Frame 0, and every frame with no accepted frame in front of it, takes the first arg-max of P over all bins.  Every other frame
+ *     takes the first maximum over the 2·span + 1 bins b − span … b + span (mod N), walked in that order, b the bin of the last accepted
+ *     frame.  span = 0: every frame searches all bins.  c, l, r, the interpolation, tune and quality = c / mean(P over ALL bins) are
+ *     lsdr_tune_est's step 5 and 7 on the peak's cyclic neighbours (which may lie outside the gate).
+ *   4 ACCEPT OR HOLD.  A frame with quality ≥ min_quality is accepted.  Any other frame is held: its record is written with held = 1, it
+ *     is no knot of the track, and it does not move b.
+ * A frame's record carries center = s_k + blocks·N/2, the sample its tune belongs to.  The summary is taken over the accepted frames in
+ * frame order.  With `blocks` equal on both sides, frame 0's record is lsdr_tune_est's record of the same capture, field for field and
+ * bit for bit.  The accepted frames' (center, tune) are the knots lsdr_derotate_batch takes.
+ * LIMITS: QPSK only; |f| < 1/8; a narrow-band interferer inside the gate wins the peak; the carrier should move by less than about one bin
+ * of the fourth power per block inside a frame (1.5e-8 cycles per sample²), or the line smears over the frame's blocks.
+ * A capture's records are a pure function of its converted samples: no atomics, every sum in a fixed order — bit for bit the same alone,
+ * in any batch, at any place of it, and in every format that converts to the same floats.
+ * run_async queues everything on the context's stream and returns: one launch over all blocks of all frames of all captures (one
+ * workgroup per block; blocks × 16 KB of scratch per frame), one over the frames (a frame's rows summed in block order, its first maximum
+ * over all bins), one over the captures (one workgroup walks a capture's frames in order: the gate makes that serial, and only the gate's
+ * 2·span + 1 bins are read there), the records' copy to pinned memory.  wait is one event synchronisation and the read of the records.  One run in
+ * flight per object.  Pointers as for lsdr_tune_est; nothing behind a capture's last whole block is read.
+ * LSDR_E_ARG, with a message, the object (if any) left usable: n_captures outside 1 … 65535, in_format outside the five LSDR_IN_*,
+ * in_scale or min_quality negative or not finite, blocks > 16, hop not a multiple of 4096, span > 2047, nonzero reserved; a capture with
+ * more than max_frames frames (checked before anything is queued), a misaligned pointer, samples without a pointer, run_async with a run
+ * in flight, wait with none. */
+typedef struct lsdr_tune_track lsdr_tune_track;
+typedef struct {
+  int n_captures;      /* B */
+  int in_format;       /* LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32 */
+  float in_scale;      /* as lsdr_tune_est_cfg.in_scale */
+  unsigned blocks;     /* blocks of 4096 samples per frame, at most 16; 0 = 4 */
+  unsigned hop;        /* samples between two frames' starts, a multiple of 4096; 0 = 65536 */
+  unsigned span;       /* the gate: ± span bins of 1/(4·4096) cycles per sample around the last accepted peak, at most 2047; 0 = no gate */
+  float min_quality;   /* a frame below it is held; 0 = 30 */
+  unsigned max_frames; /* of one capture; 0 = 256.  Scratch: n_captures × max_frames × blocks rows of 16 KB */
+  int reserved[4];     /* 0 */
+} lsdr_tune_track_cfg; /* 48 bytes */
+typedef struct {
+  uint64_t center;     /* s_k + blocks·4096/2: the sample the frame's tune belongs to */
+  float tune;          /* cycles per sample, as lsdr_tune_estimate.tune */
+  float quality;       /* power[1] / mean_power */
+  uint32_t bin;        /* the peak's bin, 0 … 4095 */
+  uint32_t held;       /* 1: quality < min_quality — no knot, the gate stays */
+  float power[3];      /* l, c, r */
+  float mean_power;    /* mean(P) over all bins */
+} lsdr_track_frame;    /* 40 bytes */
+typedef struct {
+  uint32_t frames, accepted;
+  float tune_first, tune_last, tune_min, tune_max, quality_min;   /* over the accepted frames; all zero where there is none */
+} lsdr_track_summary;  /* 28 bytes */
+int lsdr_tune_track_create(lsdr_ctx *ctx, const lsdr_tune_track_cfg *cfg, lsdr_tune_track **t);
+void lsdr_tune_track_destroy(lsdr_tune_track *t);
+unsigned lsdr_tune_track_max_frames(const lsdr_tune_track *t);      /* with the default filled in */
+int lsdr_tune_track_run_async(lsdr_tune_track *t, const void *const *iq_dev, const size_t *n_samples /* [B], host */);
+/* frames: [B][max_frames], capture i's records at frames[i·max_frames … + summary[i].frames); may be NULL */
+int lsdr_tune_track_wait(lsdr_tune_track *t, lsdr_track_summary *summary /* [B] */, lsdr_track_frame *frames);
+
+/* ------------------------------------------------------------ a track, given, taken out of the samples
+ * lsdr_derotate_batch multiplies every capture by exp(−j·2π·φ(n)), φ the integral of a piecewise-linear frequency track, and writes cf32
+ * items that lsdr_capture_batch decodes as LSDR_IN_CF32 (in_scale 1) with tune 0.  The track is GIVEN by the caller as knots
+ * (sample, tune), exactly as lsdr_capture_each.tune is given: from lsdr_tune_track's accepted frames, from an orbit prediction, or from a
+ * smoothing of either.  Per capture: samples strictly ascending and below 2^31, |tune| < 0.5, |Δtune| between neighbours < 0.5.
+ *
+ * THE DEFINITION.  All phase arithmetic is in integers, in units of 2^-64 cycle, wrapping modulo 2^64 (tests/track_common.py restates it
+ * in Python integers):
+ *   frequency word  F_i = (int64) of ldexp(tune_i, 64) rounded to nearest (for |tune| > 2^-11 the double is a whole number already);
+ *   slope of segment i, between knot i and knot i + 1:  S_i = floor((F_{i+1} − F_i) / (sample_{i+1} − sample_i)), signed floor division;
+ *   outside the knots the first segment's slope runs back to sample 0 and the last one's runs on to the end: where knot 0 is not on
+ *     sample 0, the library puts a knot at sample 0 with F = F_0 − S_0·sample_0, and the last knot starts a segment with the slope in
+ *     front of it.  One knot: a constant frequency.  No knots: F = 0, the capture passes through converted;
+ *   phase  φ(n) = Φ_i + F_i·m + S_i·(m(m − 1)/2), m = n − sample_i, i the last knot at or before n; Φ at sample 0 is 0 and
+ *     Φ_{i+1} = φ_i(sample_{i+1}): the phase is continuous, the frequency steps by less than sample_{i+1} − sample_i units at a knot;
+ *   rotation  (c, s) = lsdr_trig16_table's entry φ(n) >> 48: cosf / sinf of 2π·index/65536;
+ *   output  out.re = xr·c + xi·s, out.im = xi·c − xr·s in float32, every product and sum rounded on its own; x the converted sample,
+ *     float(item − Z)·in_scale.
+ * The sign is lsdr_capture_each.tune's: a capture multiplied by exp(+j2π·Σf) comes back with knots of +f.
+ * The host turns a capture's knots into its (Φ, F, S) table and uploads it with the run; one launch covers all captures, every one with
+ * its own length; 16-byte loads (where the capture's pointer is 16-byte aligned) and 16-byte stores.  Nothing behind item n − 1 is read
+ * or written.  A capture's output is a pure function of its samples and its knots.  One run in flight per object.
+ * The cf32 copy costs 8 bytes of device memory per sample.  What is left of the carrier after the derotation must still fit the decoder's
+ * tuning window.
+ * LSDR_E_ARG, with a message, the object left usable: knots out of order, a knot's sample ≥ 2^31, a tune not finite or outside
+ * (−0.5, 0.5), a step of 0.5 or more between neighbours, a pointer not aligned to its item, an output pointer not aligned to 16 bytes,
+ * samples without a pointer, n_samples above max_samples, more than max_knots knots, a table above 2^22 segments at create, nonzero
+ * reserved, run_async with a run in flight, wait with none. */
+typedef struct lsdr_derotate_batch lsdr_derotate_batch;
+typedef struct { uint64_t sample; double tune; } lsdr_track_knot;   /* 16 bytes */
+typedef struct {
+  int n_captures;      /* B, 1 … 65535 */
+  int in_format;       /* LSDR_IN_CU8, _CS8, _CU16, _CS16, _CF32 */
+  float in_scale;      /* as lsdr_capture_input_cfg.in_scale: 0 or 1 = none */
+  unsigned max_knots;  /* of one capture, at most 2^20; n_captures × (max_knots + 1) at most 2^22 (32 bytes of table each) */
+  size_t max_samples;  /* of one capture */
+  int reserved[4];     /* 0 */
+} lsdr_derotate_batch_cfg;  /* 40 bytes */
+typedef struct {
+  size_t n_samples;
+  const lsdr_track_knot *knots;   /* HOST, n_knots of them; read during run_async only */
+  unsigned n_knots;
+  unsigned reserved;   /* 0 */
+} lsdr_derotate_each;  /* 24 bytes */
+int lsdr_derotate_batch_create(lsdr_ctx *ctx, const lsdr_derotate_batch_cfg *cfg, lsdr_derotate_batch **b);
+void lsdr_derotate_batch_destroy(lsdr_derotate_batch *b);
+/* iq_dev, out_dev: HOST arrays of B DEVICE pointers; out_dev[i] 16-byte aligned with room for each[i].n_samples items */
+int lsdr_derotate_batch_run_async(lsdr_derotate_batch *b, const void *const *iq_dev, const lsdr_derotate_each *each /* [B], host */,
+                                  lsdr_cf32 *const *out_dev);
+int lsdr_derotate_batch_wait(lsdr_derotate_batch *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -407,6 +407,58 @@ _sig("lsdr_tune_est_run_async", C.c_int, [vp, vp, psz])
 _sig("lsdr_tune_est_wait", C.c_int, [vp, C.POINTER(TuneEstimate)])
 
 
+class TuneTrackCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("in_format", C.c_int), ("in_scale", C.c_float), ("blocks", C.c_uint), ("hop", C.c_uint),
+                ("span", C.c_uint), ("min_quality", C.c_float), ("max_frames", C.c_uint), ("reserved", C.c_int * 4)]
+
+
+class TrackFrame(C.Structure):
+    """lsdr_track_frame: one frame of a capture's carrier track."""
+    _fields_ = [("center", C.c_uint64), ("tune", C.c_float), ("quality", C.c_float), ("bin", C.c_uint32), ("held", C.c_uint32),
+                ("power", C.c_float * 3), ("mean_power", C.c_float)]
+
+    def as_dict(self):
+        return dict(center=int(self.center), tune=float(self.tune), quality=float(self.quality), bin=int(self.bin), held=int(self.held),
+                    power=[float(v) for v in self.power], mean_power=float(self.mean_power))
+
+
+class TrackSummary(C.Structure):
+    """lsdr_track_summary: a capture's track over its accepted frames."""
+    _fields_ = [("frames", C.c_uint32), ("accepted", C.c_uint32), ("tune_first", C.c_float), ("tune_last", C.c_float),
+                ("tune_min", C.c_float), ("tune_max", C.c_float), ("quality_min", C.c_float)]
+
+    def as_dict(self):
+        return dict(frames=int(self.frames), accepted=int(self.accepted), tune_first=float(self.tune_first), tune_last=float(self.tune_last),
+                    tune_min=float(self.tune_min), tune_max=float(self.tune_max), quality_min=float(self.quality_min))
+
+
+_sig("lsdr_tune_track_create", C.c_int, [vp, C.POINTER(TuneTrackCfg), C.POINTER(vp)])
+_sig("lsdr_tune_track_destroy", None, [vp])
+_sig("lsdr_tune_track_max_frames", C.c_uint, [vp])
+_sig("lsdr_tune_track_run_async", C.c_int, [vp, vp, psz])
+_sig("lsdr_tune_track_wait", C.c_int, [vp, C.POINTER(TrackSummary), C.POINTER(TrackFrame)])
+
+
+class TrackKnot(C.Structure):
+    """lsdr_track_knot: the carrier offset `tune` (cycles per sample) at `sample`."""
+    _fields_ = [("sample", C.c_uint64), ("tune", C.c_double)]
+
+
+class DerotateBatchCfg(C.Structure):
+    _fields_ = [("n_captures", C.c_int), ("in_format", C.c_int), ("in_scale", C.c_float), ("max_knots", C.c_uint), ("max_samples", C.c_size_t),
+                ("reserved", C.c_int * 4)]
+
+
+class DerotateEach(C.Structure):
+    _fields_ = [("n_samples", C.c_size_t), ("knots", C.POINTER(TrackKnot)), ("n_knots", C.c_uint), ("reserved", C.c_uint)]
+
+
+_sig("lsdr_derotate_batch_create", C.c_int, [vp, C.POINTER(DerotateBatchCfg), C.POINTER(vp)])
+_sig("lsdr_derotate_batch_destroy", None, [vp])
+_sig("lsdr_derotate_batch_run_async", C.c_int, [vp, vp, C.POINTER(DerotateEach), vp])
+_sig("lsdr_derotate_batch_wait", C.c_int, [vp])
+
+
 class RateEstCfg(C.Structure):
     _fields_ = [("n_captures", C.c_int), ("in_format", C.c_int), ("in_scale", C.c_float), ("blocks", C.c_uint), ("omega_min", C.c_float),
                 ("omega_max", C.c_float), ("reserved", C.c_int * 2)]
@@ -1846,10 +1898,13 @@ class RecordingDecoder:
     (recording_plan), decoded pieces_per_batch at a time as the captures of one batch (CaptureBatch, in either engine, or HsBatch with
     hs=True — each piece acquires anew), and the pieces' TS joined on the device (TsStitch, with `window` and `min_run`), the join between
     the last piece of one batch and the first of the next included.  tune: leandvb's --tune as Ftune/Fs in cycles per sample for every
-    piece; None: estimated once, from the first piece (TuneEstimator; 0 where its quality is below TUNE_MIN_QUALITY).
+    piece; None: estimated once, from the first piece (TuneEstimator; 0 where its quality is below TUNE_MIN_QUALITY); "pieces": every
+    piece gets its own, estimated from its own first blocks by one TuneEstimator run in front of each batch — a piece below
+    TUNE_MIN_QUALITY takes its left neighbour's (the recording's first piece: 0) — for recordings whose carrier wanders from piece to piece;
+    within a piece it must still stay inside the tiles' window.
     decode / decode_file return (the TS's bytes, report): report = dict(pieces: [dict(first_sample, n_samples, result, keep: [start, end)
     of the piece's TS, ts: its bytes with piece_ts=True, head_in_front: see below)], joins: [dict(joined, run, end, next_start)] per adjacent pair, unjoined: the
-    indices of the pairs that did not join, tune, packets).  The TS is the stitch's output with one exception: where the left piece of a join is kept
+    indices of the pairs that did not join, tune, tunes: the tune of every piece, packets).  The TS is the stitch's output with one exception: where the left piece of a join is kept
     from its first packet and holds fewer packets in front of the run than the right piece (it acquired late, behind a fade, beside a
     neighbour that started in the clear), the right piece's packets in front of the run go out in place of the left piece's: the left
     piece's record gains head_in_front (the packets taken from its neighbour) and dropped_in_front (its own, left out)."""
@@ -1867,7 +1922,7 @@ class RecordingDecoder:
         num, den = (1, 2) if hs else FEC_RATE[fec]
         # a piece's packets: its symbols carry 2·rate bits each, a packet is 204·8 of them; 1 % and 64 packets of room (omega is nominal)
         self.max_packets = int(1.01 * self.piece / float(omega) * 2 * num / den / 1632) + 64
-        self._parts, self._bufs, self._est = [], [], None
+        self._parts, self._bufs, self._est, self._est_pieces = [], [], None, None
         try:
             if hs:
                 self.batch = self._own(HsBatch(ctx, self.B, self.piece, omega, **batch_kw))
@@ -1903,9 +1958,10 @@ class RecordingDecoder:
             b.free()
         for p in getattr(self, "_pinned", []):
             lib.lsdr_free_host(p)
-        if self._est:
-            self._est.close()
-        self._parts, self._bufs, self._pinned, self._carry, self._est = [], [], [], None, None
+        for e in (self._est, self._est_pieces):
+            if e:
+                e.close()
+        self._parts, self._bufs, self._pinned, self._carry, self._est, self._est_pieces = [], [], [], None, None, None
 
     def plan(self, n_samples):
         """recording_plan with this object's piece and overlap."""
@@ -1916,6 +1972,8 @@ class RecordingDecoder:
         return pieces[0][0], pieces[-1][0] + pieces[-1][1]
 
     def _tune_of(self, ptr, n):
+        if self.tune == "pieces":
+            return "pieces"
         if self.tune is not None:
             return float(self.tune)
         if not self._est:
@@ -1924,12 +1982,27 @@ class RecordingDecoder:
         return e["tune"] if e["quality"] >= TUNE_MIN_QUALITY else 0.0
 
     def _start(self):
-        return dict(pieces=[], joins=[], unjoined=[], tune=None, packets=0), [], None
+        return dict(pieces=[], joins=[], unjoined=[], tune=None, tunes=[], packets=0), [], None
 
-    def _batch_async(self, base_ptr, first_sample, pieces, tune):
+    def _piece_tunes(self, ptrs, lengths, left):
+        """Every piece's own tune (one TuneEstimator run over the batch); a piece without a line takes its left neighbour's, the batch's
+        first piece `left`."""
+        if not self._est_pieces:
+            self._est_pieces = TuneEstimator(self.ctx, self.B, self.in_format, self.in_scale)
+        tunes = []
+        for e in self._est_pieces.estimate(ptrs, lengths):
+            left = e["tune"] if e["quality"] >= TUNE_MIN_QUALITY else left
+            tunes.append(left)
+        return tunes
+
+    def _batch_async(self, base_ptr, first_sample, pieces, tune, report):
         """Queues the decode of consecutive pieces; base_ptr holds the recording from first_sample on."""
         ptrs = [vp(base_ptr + (s - first_sample) * self.item) if n else None for s, n in pieces] + [None] * (self.B - len(pieces))
-        self.batch.run_each_async(ptrs, [n for _, n in pieces] + [0] * (self.B - len(pieces)), tune)
+        lengths = [n for _, n in pieces] + [0] * (self.B - len(pieces))
+        if tune == "pieces":
+            tune = self._piece_tunes(ptrs, lengths, report["tunes"][-1] if report["tunes"] else 0.0)
+        self.batch.run_each_async(ptrs, lengths, tune)
+        report["tunes"] += [float(t) for t in (tune[:len(pieces)] if isinstance(tune, list) else [tune] * len(pieces))]
 
     def _batch_finish(self, pieces, last, report, out, carry):
         """Waits for the batch, joins its pieces behind the carried one and appends what is final to `out`: everything in front of the
@@ -1991,7 +2064,7 @@ class RecordingDecoder:
         tune = self._tune_of(vp(ptr), plan[0][1])
         for g in range(0, len(plan), self.B):
             pieces = plan[g:g + self.B]
-            self._batch_async(ptr, 0, pieces, tune)
+            self._batch_async(ptr, 0, pieces, tune, report)
             carry = self._batch_finish(pieces, g + self.B >= len(plan), report, out, carry)
         return self._finish(report, out, tune)
 
@@ -2031,7 +2104,7 @@ class RecordingDecoder:
             tune = self._tune_of(vp(self._bufs[0].ptr), plan[0][1])
             for g, pieces in enumerate(groups):
                 check(lib.lsdr_copy_fence(self.ctx.h))
-                self._batch_async(self._bufs[g % 2].ptr, pieces[0][0], pieces, tune)
+                self._batch_async(self._bufs[g % 2].ptr, pieces[0][0], pieces, tune, report)
                 if g + 1 < len(groups):
                     upload(g + 1)                                        # (batch g − 1, the last reader of these two buffers, was waited for)
                 carry = self._batch_finish(pieces, g + 1 == len(groups), report, out, carry)
@@ -2290,6 +2363,159 @@ class ResampledDecoder:
             for i in range(self.n):
                 info[i]["cnr"], info[i]["cnr_center"] = measured[i]["cnr"], t_dec[i]
         return res, ts, info
+
+
+class TuneTracker:
+    """lsdr_tune_track: the carrier offset of each of n_captures captures ALONG its length (QPSK: TuneEstimator's line of the fourth power
+    on frames of `blocks` blocks every `hop` samples and at the capture's end, gated to ± span bins around the last accepted frame, frames
+    below min_quality held).  max_frames: of one capture (0: 256)."""
+
+    def __init__(self, ctx, n_captures, in_format=IN_CU8, in_scale=0.0, blocks=4, hop=65536, span=64, min_quality=TUNE_MIN_QUALITY, max_frames=0):
+        self.ctx, self.n, self.h = ctx, int(n_captures), None
+        cfg = TuneTrackCfg()
+        cfg.n_captures, cfg.in_format, cfg.in_scale, cfg.blocks, cfg.hop = self.n, int(in_format), float(in_scale), int(blocks), int(hop)
+        cfg.span, cfg.min_quality, cfg.max_frames = int(span), float(min_quality), int(max_frames)
+        h = vp()
+        check(lib.lsdr_tune_track_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.max_frames = int(lib.lsdr_tune_track_max_frames(h))
+        self._sum = (TrackSummary * self.n)()
+        self._frames = (TrackFrame * (self.n * self.max_frames))()
+
+    def close(self):
+        if self.h:
+            lib.lsdr_tune_track_destroy(self.h)
+            self.h = None
+
+    def _args(self, ptrs, lengths):
+        n = [int(v) for v in lengths]
+        if len(n) != self.n or len(ptrs) != self.n:
+            raise LsdrError(f"tune tracker: {len(ptrs)} pointers and {len(n)} lengths for {self.n} captures")
+        return (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in ptrs]), (c_sz * self.n)(*n)
+
+    def run_async(self, ptrs, lengths):
+        """Queues the track of every capture's first lengths[i] items; a pointer may be None where the length is 0."""
+        check(lib.lsdr_tune_track_run_async(self.h, *self._args(ptrs, lengths)))
+
+    def wait(self):
+        check(lib.lsdr_tune_track_wait(self.h, self._sum, self._frames))
+        out = []
+        for i, s in enumerate(self._sum):
+            d = s.as_dict()
+            d["frames"] = [self._frames[i * self.max_frames + k].as_dict() for k in range(int(s.frames))]
+            out.append(d)
+        return out
+
+    def track(self, ptrs, lengths):
+        """One run, synchronously: [dict(accepted, tune_first, tune_last, tune_min, tune_max, quality_min, frames: [dict(center, tune,
+        quality, bin, held, power [l, c, r], mean_power)])] per capture."""
+        self.run_async(ptrs, lengths)
+        return self.wait()
+
+
+def track_knots(frames):
+    """[(center, tune)] of a track's accepted frames: the knots DerotateBatch takes."""
+    return [(f["center"], f["tune"]) for f in frames if not f["held"]]
+
+
+class DerotateBatch:
+    """lsdr_derotate_batch: a carrier track, GIVEN per capture as knots [(sample, tune)], taken out of n_captures captures in one launch:
+    each capture of in_format items, with its own length, converted and multiplied by exp(−j2π·φ(n)) into a cf32 stream (what
+    CaptureBatch(in_format=IN_CF32, in_scale=1) decodes with tune 0).  The frequency runs linearly between the knots, with the first and the
+    last slope outside them; no knots: the capture passes through converted."""
+
+    def __init__(self, ctx, n_captures, max_samples, max_knots, in_format=IN_CU8, in_scale=0.0):
+        self.ctx, self.n, self.h = ctx, int(n_captures), None
+        cfg = DerotateBatchCfg()
+        cfg.n_captures, cfg.in_format, cfg.in_scale = self.n, int(in_format), float(in_scale)
+        cfg.max_knots, cfg.max_samples = int(max_knots), int(max_samples)
+        h = vp()
+        check(lib.lsdr_derotate_batch_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib.lsdr_derotate_batch_destroy(self.h)
+            self.h = None
+
+    def _args(self, ptrs, lengths, knots, outs):
+        n = [int(v) for v in lengths]
+        if not (len(n) == len(ptrs) == len(knots) == len(outs) == self.n):
+            raise LsdrError(f"derotate batch: {len(ptrs)} pointers, {len(n)} lengths, {len(knots)} tracks and {len(outs)} outputs for {self.n} captures")
+        e = (DerotateEach * self.n)()
+        keep = []
+        for i in range(self.n):
+            k = (TrackKnot * max(len(knots[i]), 1))()
+            for j, (s, t) in enumerate(knots[i]):
+                k[j].sample, k[j].tune = int(s), float(t)
+            keep.append(k)
+            e[i].n_samples, e[i].knots, e[i].n_knots = n[i], k, len(knots[i])
+        as_vp = lambda ps: (vp * self.n)(*[p if isinstance(p, vp) else vp(p) for p in ps])
+        return as_vp(ptrs), e, as_vp(outs), keep
+
+    def run_async(self, ptrs, lengths, knots, outs):
+        """Queues the run: ptrs / outs device pointers per capture (None where there are no samples; outs 16-byte aligned with room for
+        lengths[i] cf32 items), knots a list of (sample, tune) per capture."""
+        p, e, o, keep = self._args(ptrs, lengths, knots, outs)
+        check(lib.lsdr_derotate_batch_run_async(self.h, p, e, o))
+
+    def wait(self):
+        check(lib.lsdr_derotate_batch_wait(self.h))
+
+    def run(self, ptrs, lengths, knots, outs):
+        self.run_async(ptrs, lengths, knots, outs)
+        self.wait()
+
+
+class TrackedDecoder:
+    """Captures whose carrier moves by more than the batch decoders' tuning window, from their raw samples to TS: track every capture's
+    carrier (TuneTracker, with tracker_kw: blocks, hop, span, min_quality), take the track out of the samples (DerotateBatch, into cf32
+    buffers of this object's: 8 bytes of device memory per sample), decode the result (CaptureBatch(in_format=IN_CF32, in_scale=1) in
+    either engine, with tune 0; batch_kw: its further arguments; relock is the default engine's and is not passed on with viterbi=, which
+    searches its alignment in front of the tail).  A capture with no accepted frame is derotated by nothing.  QPSK,
+    |offset| < 1/8 cycle per sample; what the track leaves of the carrier must fit the tiles' window."""
+
+    def __init__(self, ctx, n_captures, max_samples, omega, fec=FEC12, viterbi=None, in_format=IN_CU8, in_scale=0.0, relock=0, anf=1,
+                 batch_kw=None, **tracker_kw):
+        self.ctx, self.n, self.max_samples = ctx, int(n_captures), int(max_samples)
+        blocks, hop = int(tracker_kw.get("blocks", 4)) or 4, int(tracker_kw.get("hop", 65536)) or 65536
+        tracker_kw.setdefault("max_frames", max(1, max(0, self.max_samples - blocks * 4096) // hop + 2))
+        batch_kw = dict(batch_kw or {})
+        if relock and not viterbi:
+            batch_kw["relock"] = relock
+        self._parts, self._outs = [], []
+        try:
+            self.tracker = self._own(TuneTracker(ctx, self.n, in_format, in_scale, **tracker_kw))
+            self.derotator = self._own(DerotateBatch(ctx, self.n, self.max_samples, self.tracker.max_frames, in_format, in_scale))
+            self.batch = self._own(CaptureBatch(ctx, self.n, self.max_samples, omega, fec=fec, anf=anf, viterbi=viterbi, in_format=IN_CF32,
+                                                in_scale=1.0, **batch_kw))
+            self._outs = [ctx.alloc(max(self.max_samples, 2) * 8) for _ in range(self.n)]
+        except Exception:
+            self.close()
+            raise
+
+    def _own(self, part):
+        self._parts.append(part)
+        return part
+
+    def close(self):
+        for p in reversed(self._parts):
+            p.close()
+        for b in self._outs:
+            b.free()
+        self._parts, self._outs = [], []
+
+    def outputs(self, i, n):
+        """The first n items of capture i's derotated stream after a decode (host, complex64)."""
+        return self.ctx.download(self._outs[i], np.complex64, int(n))
+
+    def decode(self, ptrs, lengths):
+        """(results, [TS bytes per capture], tracks): tracks[i] is TuneTracker.track's record of capture i."""
+        tracks = self.tracker.track(ptrs, lengths)
+        outs = [b.ptr for b in self._outs]
+        self.derotator.run(ptrs, lengths, [track_knots(t["frames"]) for t in tracks], outs)
+        res, ts = self.batch.decode_each(outs, lengths, 0.0)
+        return res, ts, tracks
 
 
 class CarrierScan:
